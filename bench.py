@@ -1,6 +1,17 @@
 """Benchmark: walker-steps/s of the apf_step2 Gibbs/MH hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 0-4] [--mode exact|fast]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line of that measurement
+(``value``, ``ms_per_step``, the roofline arithmetic on the timed launches' HIP-event
+times, the posterior summary of the moments the timed steps folded).  ``--full`` adds the
+measurements that take runs or processes of their own: the other eval mode
+(``alt_eval``), the CPU baselines (``cpu_baseline``, ``reference_like``), the CSV
+emission figure and the SMU clock sampled over the timed launches (each still has its
+``--no-...`` switch).  ``--dump-outputs DIR`` writes what the last timed step left for
+its caller (``dump_outputs``) as ``DIR/<name>.npy``; the inputs are seeded, so two builds
+run with the same arguments can be compared array for array.
 
 A bench *step* is one launch of the fused sampler kernel: every walker on the GPU
 runs ``--iters`` Gibbs iterations (apf_step2.py:300-351: parameter draw, proposal,
@@ -458,6 +469,44 @@ def fault_drill(s, rank: int, world: int, barrier, group) -> dict:
                     "recover the same summary"}
 
 
+# bytes of array data one rank's --dump-outputs may write (64 MB in all, .npy headers
+# included)
+DUMP_BUDGET = 60 * 10 ** 6
+
+
+def dump_outputs(s, out_dir: str, rank: int = 0, moments: bool = True,
+                 seed: int = 0) -> dict:
+    """Write what the last timed step left for its caller as ``out_dir/<name>.npy``
+    (float64): the launch's recorded chain rows ``chain`` [k, nrec, PS], every walker's
+    ``state`` [k, PS] with its ``tries`` / ``accepts`` counters [k, P], and ``moments``,
+    this GPU's whole-run moment sums (olpe_moments_summary) the step's fold updated.
+    The per-walker arrays hold the same k walkers, ``walkers`` (their indices): all W
+    where that fits DUMP_BUDGET, else a sample drawn once from ``seed`` -- the same walkers
+    in every run with the same arguments, as the inputs (synthetic frame, start, walker
+    seeds) are.  Ranks after the first append ``_rank<r>`` to the names."""
+    st, tries, accs = s.get_state()
+    W = st.shape[0]
+    nrec = int(getattr(s, "_nrec", 0))
+    chain = s.chain() if nrec else np.empty((W, 0, st.shape[1]))
+    per_walker = 8 * (1 + chain.shape[1] * chain.shape[2] + st.shape[1] + 2 * tries.shape[1])
+    mom = s.moments_summary() if moments else None
+    k = max(1, min(W, (DUMP_BUDGET - (mom.nbytes if moments else 0)) // per_walker))
+    idx = (np.arange(W) if k == W else
+           np.sort(np.random.default_rng(seed).choice(W, k, replace=False)))
+    arrays = {"walkers": idx.astype(np.float64), "chain": chain[idx], "state": st[idx],
+              "tries": tries[idx], "accepts": accs[idx]}
+    if moments:
+        arrays["moments"] = mom
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if rank else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"),
+                np.ascontiguousarray(a, dtype=np.float64))
+    return {"dir": out_dir, "walkers": int(k), "of_walkers": int(W),
+            "arrays": {name: list(np.shape(a)) for name, a in arrays.items()},
+            "bytes": int(sum(np.asarray(a).size for a in arrays.values()) * 8)}
+
+
 def load_json(path: str):
     try:
         with open(path) as f:
@@ -673,6 +722,15 @@ def main():
     ap.add_argument("--stride", type=int, default=None,
                     help="chain record stride (default: the config's, DEFAULTS)")
     ap.add_argument("--mode", default="fast", choices=["exact", "fast"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the other eval mode, the "
+                         "CPU baselines, the CSV emission, the SMU clock over the timed "
+                         "launches (off by default: a plain run times its steps and prints "
+                         "the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (chain rows, "
+                         "walker state and counters, moment sums) as DIR/<name>.npy "
+                         "(bench.dump_outputs)")
     ap.add_argument("--no-alt", action="store_true",
                     help="skip the single-GPU measurement of the other eval mode")
     ap.add_argument("--cpu-steps", type=int, default=None,
@@ -730,6 +788,9 @@ def main():
     for k in ("iters", "stride", "steps", "warmup"):
         if getattr(args, k) is None:
             setattr(args, k, dflt[k])
+    if not args.full:
+        # a plain run: the timed steps and their line alone
+        args.no_alt = args.no_cpu_baseline = args.no_csv = True
     # the per-config default shape (the profiled one: profiles/valu_counts.json)
     default_shape = not args.walkers and args.iters == dflt["iters"] \
         and args.stride == dflt["stride"]
@@ -771,7 +832,9 @@ def main():
     p0[-1] = s.chi_squared(p0)
     s.seed(odist.walker_seeds(1000, rank * wpg, wpg))      # weak scaling: wpg per GPU
     s.set_state(np.tile(p0, (wpg, 1)))
-    clock = clock_meter(Sampler, placement[rank][4])   # this rank's GPU (its PCI bus id)
+    # this rank's GPU (its PCI bus id); --full only: the metrics library's set-up is no
+    # part of a plain run
+    clock = clock_meter(Sampler, placement[rank][4]) if args.full else None
 
     first_launch = []          # when this rank queued its first sampler launch
 
@@ -821,6 +884,10 @@ def main():
     units = s.last_units()          # chunks per walker of the timed launches
     st, tries, accs = s.get_state()
     acceptance = float(accs.sum() / max(1.0, tries.sum()))
+    dumped = None
+    if args.dump_outputs:
+        # before anything else launches: the last timed step's outputs
+        dumped = dump_outputs(s, args.dump_outputs, rank, moments=not args.no_moments)
     alt = None
     if world == 1 and not args.no_alt:
         other = "exact" if args.mode == "fast" else "fast"
@@ -1087,6 +1154,11 @@ def main():
 
     watchdog_cancel()
     out = report(elapsed, kernel_ms, units, acceptance, comm, alt)
+    out["full"] = args.full
+    if not args.full:
+        out["clock_note"] = "the SMU clock is sampled over the timed launches with --full only"
+    if dumped:
+        out["dump_outputs"] = dumped
     if moments is None and world == 1 and not args.exchange and not args.no_moments:
         moments = s.allreduce_moments()          # no communicator: this context alone
     if moments is not None:

@@ -79,6 +79,42 @@ def test_bench_default_line_has_posterior_and_profile():
     assert r["frac_source"] == "counters" and 0 < r["frac"] <= 1
 
 
+def test_bench_dump_outputs_are_the_last_steps(tmp_path):
+    """--dump-outputs: the arrays a plain run writes are what the sampler's caller holds
+    after the last timed launch -- the same seeds, start and launches run here give the
+    same chain rows, state, counters and moment sums (the sampler is deterministic)."""
+    import numpy as np
+    from olpefit_amd import dist, synth
+    from olpefit_amd.core import Sampler
+    from olpefit_amd.pipeline import initial_parameters
+    W = 1536
+    d = _bench("--gpus", "1", "--walkers", str(W), "--steps", "2", "--warmup", "1",
+               "--dump-outputs", str(tmp_path))
+    assert d["full"] is False and "alt_eval" not in d and "cpu_baseline" not in d
+    info = d["dump_outputs"]
+    assert info["walkers"] == info["of_walkers"] == W
+    got = {k: np.load(os.path.join(str(tmp_path), k + ".npy")) for k in info["arrays"]}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["chain"].shape == (W, 10, 17) and np.array_equal(got["walkers"], np.arange(W))
+    img, _ = synth.make_image(64, 2, 0)
+    with Sampler(img, 1.0, 1, 1, 2, nsrc=2, device=0) as s:
+        p0 = initial_parameters(img, synth.guess_values(64, 2), 2)
+        p0[-1] = s.chi_squared(p0)
+        s.seed(dist.walker_seeds(1000, 0, W))
+        s.set_state(np.tile(p0, (W, 1)))
+        s.set_eval_mode("fast")
+        for _ in range(3):
+            s.run_async(100, burn_in=0, record_stride=10)
+            s.moments_accumulate()
+        s.sync()
+        st, tries, accs = s.get_state()
+        want = {"chain": s.chain(), "state": st, "tries": tries, "accepts": accs,
+                "moments": s.moments_summary()}
+    for k, a in want.items():
+        np.testing.assert_array_equal(got[k], a, err_msg=k)
+    np.testing.assert_array_equal(got["state"], got["chain"][:, -1])
+
+
 def test_bench_gpus_flag_two_ranks_share_gpu():
     """`bench.py --gpus 2` from a plain process (no launcher environment): the parent
     starts two ranks, makes no HIP call itself, and relays rank 0's line for the two

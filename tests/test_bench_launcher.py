@@ -124,8 +124,8 @@ def test_config0_line_beside_one_core():
     env.update(OLPE_BENCH_SAMPLER="bench_stub:StubSampler", OLPE_STUB_MS="5",
                PYTHONPATH=os.pathsep.join([TESTS, REPO]))
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--config", "0",
-                        "--no-alt"], cwd=REPO, env=env, capture_output=True, text=True,
-                       timeout=300)
+                        "--full", "--no-alt"], cwd=REPO, env=env, capture_output=True,
+                       text=True, timeout=300)
     assert r.returncode == 0, r.stderr
     d = _line(r)
     c = d["config"]
@@ -268,19 +268,112 @@ def test_config3_names_its_part():
 
 def test_csv_emission_reported_outside_the_timed_region():
     """CSV emission is timed separately -- the last launch's rows of up to
-    4,096 walkers written as the reference's chain files (stub rows here)."""
-    r = _run([])
+    4,096 walkers written as the reference's chain files (stub rows here); a --full
+    figure."""
+    r = _run(["--full"])
     assert r.returncode == 0, r.stderr
     c = _line(r)["csv_emission"]
     assert c["files"] == WPG and c["rows_per_file"] == ITERS // STRIDE + 1
     assert c["bytes"] > 0 and c["ms"] > 0 and c["mb_per_s"] > 0
 
 
+def _run_plain(args):
+    """bench.py with the stub sampler and none of the --no-... switches."""
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT",
+                        "TORCHELASTIC_RUN_ID", "OLPE_BENCH_LAUNCHED")}
+    env.update(OLPE_BENCH_SAMPLER="bench_stub:StubSampler", OLPE_STUB_MS="5",
+               PYTHONPATH=os.pathsep.join([TESTS, REPO]))
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1",
+                        "--walkers", str(WPG)] + args, cwd=REPO, env=env,
+                       capture_output=True, text=True, timeout=180)
+    assert r.returncode == 0, r.stderr
+    return _line(r)
+
+
+def test_plain_run_times_its_steps_and_nothing_else():
+    """`bench.py --gpus 1 --steps N --warmup W`: the N timed steps and their line; the
+    other eval mode, the CPU baselines, the CSV emission and the clock are --full's."""
+    d = _run_plain(["--steps", "4", "--warmup", "2"])
+    assert d["full"] is False and d["steps"] == 4 and d["warmup"] == 2
+    for k in ("alt_eval", "cpu_baseline", "gpu_over_cpu", "csv_emission", "dump_outputs"):
+        assert k not in d
+    assert d["per_rank_clock_ghz"] == [None] and "clock_ghz_live" not in d["roofline"]
+    assert d["metric"] == __import__("bench").METRIC and d["unit"] == "walker-steps/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f64"
+    # --steps sets the timed launches: 4 stub launches of 5 ms, the warm-up outside them
+    assert 5.0 <= d["ms_per_step"] < 50.0
+    assert d["value"] == pytest.approx(WPG * ITERS * 4 / (d["ms_per_step"] * 4e-3), rel=1e-9)
+    assert d["posterior"]["rows_per_walker"] == (4 + 2) * ITERS // STRIDE
+
+
+def test_full_run_adds_the_other_measurements():
+    """(the CPU baselines under --full: test_config0_line_beside_one_core)"""
+    d = _run_plain(["--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"])
+    assert d["full"] is True and d["steps"] == 2
+    assert d["alt_eval"]["eval"] == "exact" and d["alt_eval"]["value"] > 0
+    assert d["csv_emission"]["files"] == WPG and d["per_rank_clock_ghz"] == [2.05]
+
+
+def test_dump_outputs_writes_the_last_steps_arrays(tmp_path):
+    """--dump-outputs DIR: float64 .npy files of the last timed step's chain rows, the
+    walkers' state and counters and the moment sums, identical from run to run."""
+    import numpy as np
+    dirs = [str(tmp_path / "a"), str(tmp_path / "b")]
+    lines = [_run_plain(["--steps", "2", "--warmup", "1", "--dump-outputs", d]) for d in dirs]
+    info = lines[0]["dump_outputs"]
+    nrec, ps = ITERS // STRIDE, 17
+    assert info["walkers"] == info["of_walkers"] == WPG
+    assert info["arrays"] == {"walkers": [WPG], "chain": [WPG, nrec, ps], "state": [WPG, ps],
+                              "tries": [WPG, 16], "accepts": [WPG, 16], "moments": [85]}
+    assert sorted(os.listdir(dirs[0])) == sorted(f"{k}.npy" for k in info["arrays"])
+    total = 0
+    for name, shape in info["arrays"].items():
+        a, b = (np.load(os.path.join(d, name + ".npy")) for d in dirs)
+        assert a.dtype == np.float64 and list(a.shape) == shape
+        np.testing.assert_array_equal(a, b)
+        total += os.path.getsize(os.path.join(dirs[0], name + ".npy"))
+    assert total <= 64 * 10 ** 6
+    # the stub's walkers carry their seed in column 0 of every row
+    chain = np.load(os.path.join(dirs[0], "chain.npy"))
+    np.testing.assert_array_equal(chain[:, -1, 0], 1000 + np.arange(WPG))
+    np.testing.assert_array_equal(np.load(os.path.join(dirs[0], "state.npy")), chain[:, -1])
+
+
+def test_dump_outputs_samples_a_large_ensemble_the_same_way_every_time(tmp_path, monkeypatch):
+    """An output above the dump's byte budget is sampled by walker: the same seeded
+    sample in every run, the same walkers in every per-walker array."""
+    import numpy as np
+    import bench
+    sys.path.insert(0, TESTS)
+    try:
+        from bench_stub import StubSampler
+    finally:
+        sys.path.remove(TESTS)
+    s = StubSampler(np.zeros((64, 64)))
+    s.seed(1000 + np.arange(500))
+    s.set_state(np.arange(17.0))
+    s.ms = 0.0
+    s.run_async(100, record_stride=10)
+    s.moments_accumulate()
+    per_walker = 8 * (1 + 10 * 17 + 17 + 2 * 16)
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 120 * per_walker + 85 * 8 + 7)   # + the moments
+    a = bench.dump_outputs(s, str(tmp_path / "a"))
+    b = bench.dump_outputs(s, str(tmp_path / "b"))
+    assert a["walkers"] == b["walkers"] == 120 and a["of_walkers"] == 500
+    assert a["bytes"] <= bench.DUMP_BUDGET
+    wa, wb = (np.load(str(tmp_path / d / "walkers.npy")) for d in "ab")
+    np.testing.assert_array_equal(wa, wb)
+    assert len(set(wa)) == 120 and np.all(np.diff(wa) > 0) and 0 <= wa[0] and wa[-1] < 500
+    np.testing.assert_array_equal(np.load(str(tmp_path / "a" / "state.npy"))[:, 0], 1000 + wa)
+    np.testing.assert_array_equal(np.load(str(tmp_path / "a" / "chain.npy"))[:, 3, 0], 1000 + wa)
+
+
 def test_per_rank_kernel_times_and_host_overhead_at_world8():
     """Verdict r04 item 5: a scaling shortfall is attributable from the line.  Rank r's
     stub launches take 20 + 2r ms, so per_rank_kernel_ms spans 20..34 and
     host_overhead_frac = 1 - max kernel ms x steps / the max-over-ranks timed region."""
-    r = _run(["--gpus", "8"], {"OLPE_STUB_MS_PER_RANK": "2"})
+    r = _run(["--gpus", "8", "--full"], {"OLPE_STUB_MS_PER_RANK": "2"})     # --full: the clock
     assert r.returncode == 0, r.stderr
     d = _line(r)
     k = d["per_rank_kernel_ms"]
@@ -300,7 +393,8 @@ def test_per_rank_kernel_times_and_host_overhead_at_world8():
 
 
 def test_one_rank_line_carries_the_attribution_fields():
-    r = _run(["--warmup", "20"])           # 0.4 s of 20 ms warm-up launches: settled
+    # 0.4 s of 20 ms warm-up launches: settled (--full: the clock is sampled)
+    r = _run(["--warmup", "20", "--full"])
     assert r.returncode == 0, r.stderr
     d = _line(r)
     assert d["per_rank_kernel_ms"]["ranks"] == pytest.approx([20.0])

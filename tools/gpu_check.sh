@@ -7,4 +7,4 @@ tools/gpu_steps.sh \
   "gpu_tests:300:python -u -m pytest tests -x -q -m gpu --timeout 120 --timeout-method thread" \
   "smoke:120:python __graft_entry__.py smoke" && \
 timeout -k 10 200 tools/pmc_valu.sh 2 fast $tag && \
-tools/gpu_steps.sh "bench:300:python bench.py --no-cpu-baseline" ${EXTRA_STEPS:+"$EXTRA_STEPS"}
+tools/gpu_steps.sh "bench:300:python bench.py --full --no-cpu-baseline" ${EXTRA_STEPS:+"$EXTRA_STEPS"}
