@@ -127,8 +127,29 @@ def build(force: bool = False, verbose: bool = True) -> str:
     return LIB
 
 
+# The tests' probe of the device primitives (tests/c/device_probe.hip): the product's
+# headers and flags, its own library, nothing of libolpe.so.
+PROBE_LIB = os.path.join(HERE, "libolpe_probe.so")
+PROBE_SRC = os.path.join(REPO, "tests", "c", "device_probe.hip")
+PROBE_DEPS = [PROBE_SRC] + [os.path.join(CSRC, f) for f in ("olpe_device.h", "exp_table.h")]
+
+
+def build_probe(force: bool = False, verbose: bool = True) -> str:
+    if (not force and os.path.exists(PROBE_LIB)
+            and all(os.path.getmtime(d) <= os.path.getmtime(PROBE_LIB) for d in PROBE_DEPS)):
+        return PROBE_LIB
+    tmp = PROBE_LIB + ".tmp"
+    cmd = [HIPCC, *FLAGS, "-I", CSRC, "-o", tmp, PROBE_SRC]
+    if verbose:
+        print("[olpefit_amd] " + " ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True)
+    os.replace(tmp, PROBE_LIB)
+    return PROBE_LIB
+
+
 if __name__ == "__main__":
     if "--print-flags" in sys.argv:      # for tools/diag_build.sh and tools/build_rev.sh
         print(" ".join(f for f in FLAGS if f not in ("-Wall", "-Wno-unused-function")))
     else:
         build(force="--force" in sys.argv)
+        build_probe(force="--force" in sys.argv)

@@ -415,7 +415,9 @@ __device__ inline void mt_seed_serial(uint32_t *key, uint32_t s) {
 // exp(x) for the FAST3 setup (guarded arguments): x = (64 k + j) ln2/64 + r with
 // |r| <= ln2/128, exp(x) = 2^k * T[j] * (1 + q(r)), q of degree 5, T = 2^(j/64) from an
 // LDS copy of c_exp2_64.  12 FP64 operations instead of ocml's 19 plus range selects;
-// <= 1.13 ulp (tools/gen_exp_table.py --check).  Arguments are clamped to [-1000, 710]
+// <= 1.33 ulp (two roundings, r^6/720 at the ends of the reduction interval; 1.26 ulp
+// measured there on the device, tests/test_gpu_device_math.py; tools/gen_exp_table.py
+// --check emulates the operations).  Arguments are clamped to [-1000, 710]
 // (underflow to 0, overflow to inf); NaN is not propagated (callers are guarded).
 // (A {hi, lo}-table, degree-6 variant reaches 0.51 ulp but, with its LDS gather in the
 // dependency chain, ran the EXACT sweep 13 % slower than ocml's exp: not used.)
@@ -521,7 +523,8 @@ __device__ __forceinline__ void sincos_small(double th, double *s, double *c) {
 
 // EXACT keeps astropy's operations (np.sin(2*theta), six divisions); FAST kernels use
 // sin(2t) = 2 sin(t) cos(t), the polynomial sincos for |theta| <= pi/4 and two
-// reciprocals (<= 2 ulp apart, within the fast tolerances of DESIGN.md §5).
+// reciprocals (cos^2 and sin 2t 2 ulp, sin^2 3 ulp apart, each within 2.3 ulp of the exact
+// value: tests/test_gpu_device_math.py; within the fast tolerances of DESIGN.md §5).
 template <bool FAST>
 __device__ __forceinline__ Trig make_trig(double th) {
   double s, c;

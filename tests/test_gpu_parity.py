@@ -132,6 +132,19 @@ def test_trajectories_match_reference(golden, lib_loaded, name, mode):
         _check_traj(tr, g, w, Lw, name, TOL[mode]["traj"])
         np.testing.assert_allclose(chain[w, :Lw], g["traj_params"][w, :Lw],
                                    rtol=TOL[mode]["traj"])
+        if mode == "fast":
+            # the FAST log-normal proposal cur * e^(w g ln10) against the reference's of
+            # the same step from the same current value (ratios new / cur where the states
+            # already differ by rounding): 1e-14 relative, derived in
+            # tests/test_gpu_fast_guards.py::test_seam_runs
+            from probe_lib import lognormal_proposal_error
+            r = tr[w, :Lw, 0].astype(int)
+            i = np.arange(Lw)
+            cur = np.vstack([g["p_init"][None], chain[w, :Lw - 1]])[i, r]
+            ref_cur = np.vstack([g["p_init"][None], g["traj_params"][w, :Lw - 1]])[i, r]
+            err, _ = lognormal_proposal_error(r, tr[w, :Lw, 1], cur, g["traj_new"][w, :Lw],
+                                              ref_cur, ora.layout(int(g["nsrc"]))[3])
+            assert err.size and err.max() <= 1e-14, (name, w, err.max())
 
 
 @pytest.mark.parametrize("mode", MODES)
