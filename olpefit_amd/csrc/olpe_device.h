@@ -7,6 +7,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+#include <utility>
+
 #include "exp_table.h"
 
 namespace olpe {
@@ -75,6 +78,30 @@ __device__ __forceinline__ double dpp_f64_any(double v) {
   const int lo = __builtin_amdgcn_mov_dpp((int)(b & 0xffffffffll), CTRL, ROW_MASK, 0xf, false);
   const int hi = __builtin_amdgcn_mov_dpp((int)(b >> 32), CTRL, ROW_MASK, 0xf, false);
   return __longlong_as_double(((long long)(unsigned)lo) | ((long long)hi << 32));
+}
+
+// x = fma(lane N of h's 16-lane row, s, x): the FP64 fma with its first factor taken
+// through DPP (row_newbcast, the one DPP control FP64 ALU instructions accept on gfx950),
+// one VALU instruction; the compiler forms v_mov_b64_dpp + v_fmac_f64 from update_dpp.
+// The product's factors and the single rounding are those of fma(s, h_N, x).  Every lane
+// of the row must be active.  Hazards the compiler does not see here: a VALU write of h
+// needs 2 wait states before this, a VALU write of EXEC 5.
+template <int N>
+__device__ __forceinline__ void fmac_bcast_f64(double &x, double h, double s) {
+  static_assert(N >= 0 && N < 16, "lane of a 16-lane row");
+  asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
+      : "+v"(x)
+      : "v"(h), "v"(s), "n"(N));
+}
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index
+// is a compile-time constant (DPP controls are immediates)
+template <class F, int... I>
+__device__ __forceinline__ void static_for_seq(F &&f, std::integer_sequence<int, I...>) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F> __device__ __forceinline__ void static_for(F &&f) {
+  static_for_seq(f, std::make_integer_sequence<int, N>{});
 }
 
 // Wave-wide sum with DPP (no LDS round trips): quad_perm [1,0,3,2] / [2,3,0,1],
@@ -1119,7 +1146,12 @@ __device__ __forceinline__ bool fast3_amp_ok(const ModelDesc<NSRC> &m, int lane,
 // FAST3's shape tables, tab[2k] = H_wide(k), tab[2k+1] = H_narrow(k), k lane-parallel.
 // `which` selects the sets recomputed (bit 0 wide, bit 1 narrow); the others are copied
 // from `from` (the table of the current state: a Gibbs step changes at most one set).
-template <int NSRC>
+// SPLIT (the 64-row samplers, htab_split): tab[k] = H_wide(k), tab[rows + k] = H_narrow(k),
+// so that one 16-byte read delivers H_wide of two rows (the 64-row sweep keeps H_narrow
+// in registers; with the interleaved layout and an 8-byte read per row that sweep ran
+// level with two 16-byte reads per row, with this one +2.8 %: profiles/r07/ab_htab_dpp.log).
+__host__ __device__ constexpr bool htab_split(int nt) { return nt == 64; }
+template <int NSRC, bool SPLIT = false>
 __device__ __forceinline__ void build_htab(const ModelDesc<NSRC> &m, double *tab,
                                            const double *from, int which, int rows, int kc,
                                            double S, int lane, ExpTab ex) {
@@ -1129,9 +1161,14 @@ __device__ __forceinline__ void build_htab(const ModelDesc<NSRC> &m, double *tab
     const double dk = (double)(k - kc);
     const double e = dk * (dk - 1.0);
     double2 h;
-    h.x = (which & 1) ? ex(-(cw2 * e)) : from[2 * k];
-    h.y = (which & 2) ? ex(-(cn2 * e)) : from[2 * k + 1];
-    reinterpret_cast<double2 *>(tab)[k] = h;
+    h.x = (which & 1) ? ex(-(cw2 * e)) : from[SPLIT ? k : 2 * k];
+    h.y = (which & 2) ? ex(-(cn2 * e)) : from[SPLIT ? rows + k : 2 * k + 1];
+    if constexpr (SPLIT) {
+      tab[k] = h.x;
+      tab[rows + k] = h.y;
+    } else {
+      reinterpret_cast<double2 *>(tab)[k] = h;
+    }
   }
   wave_sync();
 }
@@ -1432,8 +1469,8 @@ __device__ __forceinline__ double sweep_fast3(const ModelDesc<NSRC> &m, const do
         rp[0][g] = rho[g] * rho[g];
       }
     }
-    auto row4 = [&](const double2 *h, const double2 *dw) {
-      double sw[RU], sn[RU];
+    // the set sums of RU rows, and the amplitudes advanced past them
+    auto sums4 = [&](double *sw, double *sn) __attribute__((always_inline)) {
       sw[0] = av[0];
       sn[0] = av[1];
 #pragma unroll
@@ -1453,6 +1490,10 @@ __device__ __forceinline__ double sweep_fast3(const ModelDesc<NSRC> &m, const do
       }
 #pragma unroll
       for (int g = 0; g < G; ++g) av[g] = av[g] * rp[0][g];
+    };
+    auto row4 = [&](const double2 *h, const double2 *dw) {
+      double sw[RU], sn[RU];
+      sums4(sw, sn);
 #pragma unroll
       for (int r = 0; r < RU; ++r) {
         const double mod = fma(sn[r], h[r].y, fma(sw[r], h[r].x, bg));
@@ -1461,7 +1502,62 @@ __device__ __forceinline__ double sweep_fast3(const ModelDesc<NSRC> &m, const do
       }
     };
     constexpr int BLK = 4;
-    if (!WRITE && NT != 0 && rows % BLK == 0) {
+    if constexpr (NT == 64 && !WRITE) {
+      // 64 rows, lane = column, every lane active: the narrow table's 64 rows live in
+      // four registers per lane (register q holds H_narrow(16 q + lane % 16): each
+      // 16-lane row a copy of 16 table rows), loaded once per sweep, and table row r
+      // enters the outer fma through a DPP broadcast of lane r % 16 of register r / 16
+      // (fmac_bcast_f64: the addend fma(sw, H_wide, bg) is a fresh temporary, so the
+      // destructive form costs no move) -- the fmas, their operands and roundings are
+      // those of row4.  Only H_wide is still read from LDS, 16 bytes per two rows
+      // (build_htab's split layout).  Prefetch as below: cutout rows one block ahead,
+      // and with HPF the wide rows too.  The table registers are dead after the last row.
+      static_assert(htab_split(NT), "table layout");
+      const double2 *p = DW + jj;
+      const double *hl = htab + 64 + (lane & 15);
+      double hnar[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) hnar[q] = hl[16 * q];
+      // H_wide of rows b0 .. b0 + 3
+      auto wide4 = [&](int b0, double *w) __attribute__((always_inline)) {
+        const double2 a = hr[b0 / 2], b = hr[b0 / 2 + 1];
+        w[0] = a.x; w[1] = a.y; w[2] = b.x; w[3] = b.y;
+      };
+      double2 cur[BLK], nxt[BLK];
+      double hw[BLK], hwn[BLK];
+#pragma unroll
+      for (int k = 0; k < BLK; ++k) cur[k] = p[k * 64];
+      if constexpr (HPF) wide4(0, hw);
+      static_for<64 / BLK>([&](auto B) __attribute__((always_inline)) {
+        constexpr int b0 = decltype(B)::value * BLK;
+        constexpr bool more = b0 + BLK < 64;
+        if constexpr (more) {
+#pragma unroll
+          for (int k = 0; k < BLK; ++k) nxt[k] = p[(b0 + BLK + k) * 64];
+          if constexpr (HPF) wide4(b0 + BLK, hwn);
+        }
+        if constexpr (!HPF) wide4(b0, hw);
+        static_for<BLK / RU>([&](auto K) __attribute__((always_inline)) {
+          constexpr int r0 = b0 + decltype(K)::value * RU;
+          double sw[RU], sn[RU];
+          sums4(sw, sn);
+          static_for<RU>([&](auto R) __attribute__((always_inline)) {
+            constexpr int r = decltype(R)::value, i = r0 + r;
+            double mod = fma(sw[r], hw[i - b0], bg);
+            fmac_bcast_f64<i % 16>(mod, hnar[i / 16], sn[r]);
+            const double t = fma(-mod, cur[i - b0].y, cur[i - b0].x);
+            acc = act ? fma(t, t, acc) : acc;
+          });
+        });
+        if constexpr (more) {
+#pragma unroll
+          for (int k = 0; k < BLK; ++k) {
+            cur[k] = nxt[k];
+            if constexpr (HPF) hw[k] = hwn[k];
+          }
+        }
+      });
+    } else if (!WRITE && NT != 0 && rows % BLK == 0) {
       const int rstep = cw.S * n;
       const double2 *p = DW + cw.grp * n + jj;
       double2 cur[BLK], nxt[BLK];
@@ -1830,8 +1926,9 @@ __device__ __forceinline__ double sweep(const ModelDesc<NSRC> &m, const double2 
     if (ok3) {
       const int tw = 2 * rows0;                            // doubles per slot
       const double *h;
+      constexpr bool HS = htab_split(NT) && !WRITE;        // the layout sweep_fast3 reads
       if (!hc) {
-        build_htab<NSRC>(m, vtab, vtab, 3, rows0, kc, (double)cw.S, lane, ExpTab{etab});
+        build_htab<NSRC, HS>(m, vtab, vtab, 3, rows0, kc, (double)cw.S, lane, ExpTab{etab});
         h = vtab;
       } else if (hc->single) {
         // in place: this step's set (the proposal's) and the sets left stale by earlier
@@ -1839,20 +1936,20 @@ __device__ __forceinline__ double sweep(const ModelDesc<NSRC> &m, const double2 
         // another sweep); the other set stays
         const int need = (hc->valid ? hc->stale : 3) | (hc->grp ? (hc->grp == 1 ? 2 : 1) : 0);
         if (need)
-          build_htab<NSRC>(m, vtab, vtab, need, rows0, kc, (double)cw.S, lane, ExpTab{etab});
+          build_htab<NSRC, HS>(m, vtab, vtab, need, rows0, kc, (double)cw.S, lane, ExpTab{etab});
         hc->valid = 1;
         hc->stale = 0;
         hc->flip = hc->grp != 0;
         h = vtab;
       } else if (hc->grp == 0) {
         if (!hc->valid) {
-          build_htab<NSRC>(m, vtab + hc->cur * tw, vtab, 3, rows0, kc, (double)cw.S, lane, ExpTab{etab});
+          build_htab<NSRC, HS>(m, vtab + hc->cur * tw, vtab, 3, rows0, kc, (double)cw.S, lane, ExpTab{etab});
           hc->valid = true;
         }
         h = vtab + hc->cur * tw;
       } else {
         double *dst = vtab + (hc->cur ^ 1) * tw;
-        build_htab<NSRC>(m, dst, vtab + hc->cur * tw, hc->valid ? (hc->grp == 1 ? 2 : 1) : 3,
+        build_htab<NSRC, HS>(m, dst, vtab + hc->cur * tw, hc->valid ? (hc->grp == 1 ? 2 : 1) : 3,
                          rows0, kc, (double)cw.S, lane, ExpTab{etab});
         hc->flip = true;
         h = dst;
