@@ -1,7 +1,9 @@
 """LAPF 3-source step 3 front end (3body/apf_step3_3body.py's arguments, read of the
-20-column chains and Gelman-Rubin statistics; see olpefit_amd/step3.py).
+20-column chains and Gelman-Rubin statistics; with --astrometry also the separation /
+position angle / RA / Dec of b and c about a, on the GPU; see olpefit_amd/step3.py).
 
     python 3body/apf_step3_3body.py <image> <system> -s <walkers> [-a <burn>]
+        [--astrometry [--distortion X.fits Y.fits] [--delta-r MAS] [--prepost pre|post]]
 """
 import os
 import sys

@@ -1,8 +1,10 @@
 """LAPF step 3 front end on MI355X output -- the reference apf_step3.py's arguments, chain
-read, burn-in and Gelman-Rubin statistics (its distortion / refraction stages need data
-the reference does not ship; see olpefit_amd/step3.py).
+read, burn-in and Gelman-Rubin statistics; with --astrometry also its separation /
+position-angle / RA / Dec summary, reduced on the GPU (the distortion tables, which the
+reference does not ship, and deltaR are inputs; see olpefit_amd/step3.py).
 
     python apf_step3.py <dir>/N2.<date>.<frame>.LDIF.fits <system> -s <walkers> [-a <burn>]
+        [--astrometry [--distortion X.fits Y.fits] [--delta-r MAS] [--prepost pre|post]]
 """
 import os
 import sys

@@ -293,6 +293,74 @@ int olpe_moments_set(olpe_ctx *ctx, long long n, const double *mean, const doubl
 #define OLPE_MOMENTS_LEN(ps, np) (2 + 3 * (ps) + 2 * (np))
 int olpe_moments_summary(olpe_ctx *ctx, const double *centre, double *out);
 
+/* --- separation / position-angle posteriors ----------------
+ * What step 3 is run for: the median and scatter of the companion's separation (mas) and
+ * position angle (deg) and its delta RA / Dec, apf_step3.py:211-256, :283-343, :401-450
+ * (3body/apf_step3_3body.py:247-288, :315-390, :450-518).  The chain rows are turned into
+ * (sep, pa) samples and reduced on the device, so a large run needs neither its chain
+ * files nor a host pass over them.  An olpe_astrom belongs to a device, not to a sampler
+ * context: step 3 uses it on chains read from files as well.  Calls on one object are not
+ * thread-safe.  Not covered: computing deltaR (the name resolver, the AltAz transform and
+ * atm_corr, :348-391), medians over several objects, and the photometry (:452-511). */
+typedef struct olpe_astrom olpe_astrom;
+/* Doubles per pair of olpe_astrom_finalize's output:
+ *   [0] np.median(sep_corrected), [1] np.std(sep_corrected)              (:436)
+ *   [2] np.median(pa_angle),      [3] np.std(pa_angle)                   (:437)
+ *   [4] RA = -np.mean(RA), [5] np.std(RA), [6] Dec = np.mean(Dec), [7] np.std(Dec)
+ *       (:446-450; variant 3 swaps sin / cos and does not negate, 3body :508-518)
+ *   [8] np.mean(pa) as :401 sees it (after :340-341), [9] the branch taken (OLPE_ASTROM_*),
+ *   [10] samples (rows x walkers), [11] 1 if :340-341 added 360
+ *   [12..15] np.mean of the de-distorted x / y of the primary, x / y of the companion
+ *       (:250-253; what :365-366 feeds to the refraction term). */
+#define OLPE_ASTROM_LEN 16
+#define OLPE_ASTROM_BELOW_180 0        /* :402 with mean(pa) >= 90: + 180 (:413) */
+#define OLPE_ASTROM_BELOW_0 1          /* :402 with mean(pa) < 90 (:415) */
+#define OLPE_ASTROM_ABOVE_360 2        /* :425 (3body :481): + 360 */
+#define OLPE_ASTROM_ABOVE_180 3        /* :427 (3body :483): + 180 */
+#define OLPE_ASTROM_ABOVE_0 4          /* :430 (3body :486) */
+#define OLPE_ASTROM_BELOW_PER_SAMPLE 5 /* 3body :462: + 180 where pa_angle < 0 */
+/* The set-up of :211-253 and :283-337 for one frame:
+ *   variant        2 (apf_step3.py: one pair) or 3 (3body: b - a and c - a)
+ *   ps, pair_cols  doubles per chain row; per pair the columns {x, y of the primary, x, y
+ *                  of the companion} (variant 2: {0,1,2,3}; 3: {0,1,2,3, 0,1,4,5}), npairs
+ *                  = variant - 1
+ *   x_dist/y_dist  the distortion look-up tables (:218-231), f64 [tab_ny][tab_nx], copied
+ *                  to the device; both NULL: no correction (the tables are not shipped)
+ *   xdiff/ydiff    the index offsets of :241-242
+ *   pixscale       mas per pixel (:224 / :231); rotation_angle :300 / :302; rotcorr :334,
+ *                  added only if use_rotcorr != 0 (ROTMODE 'vertical angle', :309)
+ *   walkers, row_cap  the store holds row_cap rows of every walker (2 doubles per walker,
+ *                  row and pair).
+ * A sample whose position is non-finite or whose table index falls outside the table
+ * (where the reference raises, or wraps a negative index) is never used as an index: it
+ * is counted, and olpe_astrom_finalize fails.  Invalid arguments are OLPE_EINVAL before
+ * any GPU call; a failed allocation is OLPE_ENOMEM naming its bytes. */
+int olpe_astrom_create(int device, int variant, int ps, const int *pair_cols, int npairs,
+                       const double *x_dist, const double *y_dist, int tab_ny, int tab_nx,
+                       int xdiff, int ydiff, double pixscale, double rotation_angle,
+                       double rotcorr, int use_rotcorr, long long walkers, long long row_cap,
+                       olpe_astrom **out);
+void olpe_astrom_destroy(olpe_astrom *a);
+/* :211-256, :283-304, :337 for the rows of ctx's last launch, read from its device chain
+ * (async on the context's stream, no host copy).  Once per launch (OLPE_ESTATE if this
+ * launch was folded already); OLPE_ESTATE if the store would overflow. */
+int olpe_astrom_fold_ctx(olpe_astrom *a, olpe_ctx *ctx);
+/* The same for host rows [nrows][walkers][ps] as step 3 collates them (:169-205,
+ * step3.load_chains); only the position columns are uploaded. */
+int olpe_astrom_fold_rows(olpe_astrom *a, const double *rows, long long nrows);
+/* Rows folded per walker so far. */
+int olpe_astrom_rows(olpe_astrom *a, long long *rows);
+/* :340-341, :401-450 (3body :383-386, :450-518) over every folded sample, with the
+ * differential refraction deltaR (mas; :391) and PARANTEL (:393) given: out
+ * [npairs][OLPE_ASTROM_LEN].  Every sum runs over the store in a fixed order, so the
+ * result does not depend on how the rows were split over folds.  The store then holds
+ * (sep_corrected, pa_angle): one finalize per object.  OLPE_EINVAL, with the count, if
+ * any sample was unusable (see olpe_astrom_create). */
+int olpe_astrom_finalize(olpe_astrom *a, double delta_r, double parantel, double *out);
+/* After finalize: the device's sep_corrected into out[0 .. n) and pa_angle into
+ * out[n .. 2n), n = rows x walkers, sample (row r, walker w) at r * walkers + w. */
+int olpe_astrom_samples(olpe_astrom *a, int pair, double *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -85,6 +85,14 @@ SIGNATURES = {
     "olpe_comm_allgather_chain": (_i, [_P, _ll, _ll, _pd, _pll]),
     "olpe_comm_gather_limit": (_i, [_P, _ll]),
     "olpe_comm_allreduce_moments": (_i, [_P, _pd]),
+    "olpe_astrom_create": (_i, [_i, _i, _i, C.POINTER(_i), _i, _pd, _pd, _i, _i, _i, _i,
+                                _d, _d, _d, _i, _ll, _ll, C.POINTER(_P)]),
+    "olpe_astrom_destroy": (None, [_P]),
+    "olpe_astrom_fold_ctx": (_i, [_P, _P]),
+    "olpe_astrom_fold_rows": (_i, [_P, _pd, _ll]),
+    "olpe_astrom_rows": (_i, [_P, _pll]),
+    "olpe_astrom_finalize": (_i, [_P, _d, _d, _pd]),
+    "olpe_astrom_samples": (_i, [_P, _i, _pd]),
     "olpe_moments_fault": (_i, [_P, _i]),
     "olpe_test_hold_handoff": (_i, [_P, _i]),
 }

@@ -2,8 +2,10 @@
 
 apf_step3.py reads the step-2 chain files (:169-186), drops ``additional_burnin`` rows
 (:81-84, :190-205; default 1 = the NaN seed row) and computes Gelman-Rubin statistics
-with d = 16 (:258-278) before its (out-of-scope) distortion / refraction / plotting
-stages.  This module is that read + statistics front end, usable on the build's output.
+with d = 16 (:258-278) before its distortion / refraction / plotting stages.  This
+module is that read + statistics front end, usable on the build's output; with
+``--astrometry`` it goes on to the separation / position-angle summary (:211-256,
+:283-343, :401-450), reduced on the GPU (olpefit_amd/astrometry.py).
 """
 from __future__ import annotations
 
@@ -175,10 +177,10 @@ def main(argv=None, nsrc: int = 2):
     loader), its burn-in slice (:190-205) and its Gelman-Rubin statistics (:258-278),
     printed as the reference prints them, then per-parameter mean / median / sigma and
     the acceptance (``posterior_summary.json`` when step 2 wrote one), written to
-    ``<frame>_apf_results/step3_summary.json``.  The distortion, refraction and
-    separation / PA stages after :278 need the NIRC2 distortion tables the reference
-    does not ship and a network name resolver: out of scope.
-    ``--from-moments`` skips the chain files and uses step 2's device moments."""
+    ``<frame>_apf_results/step3_summary.json``.
+    ``--from-moments`` skips the chain files and uses step 2's device moments.
+    ``--astrometry`` adds the separation / position-angle stages after :278 (``astrometry``
+    below); without it nothing past the statistics runs and the outputs are unchanged."""
     import argparse
     import json
     import sys
@@ -195,6 +197,17 @@ def main(argv=None, nsrc: int = 2):
                          "additional_burnin 1) instead of the chain files")
     ap.add_argument("--npy", action="store_true", help="read the {i}_chain.npy sidecars")
     ap.add_argument("-q", "--quiet", action="store_true")
+    ap.add_argument("--astrometry", action="store_true",
+                    help="separation / position angle / RA / Dec of the chains (GPU); appends "
+                         "to epoch_grand_pasep and epoch_grand_radec beside the image")
+    ap.add_argument("--distortion", nargs=2, metavar=("X.fits", "Y.fits"),
+                    help="the NIRC2 distortion look-up tables (not shipped; without them no "
+                         "distortion correction is applied)")
+    ap.add_argument("--delta-r", type=float, default=0.0, metavar="MAS",
+                    help="differential refraction deltaR in mas (apf_step3.py:391; default 0)")
+    ap.add_argument("--prepost", choices=("pre", "post"),
+                    help="distortion epoch (default: from the year the image's directory "
+                         "name starts with, apf_step3.py:149-153)")
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
     say = (lambda *a: None) if args.quiet else print
     ncor = int(np.int_(args.size))                                  # :76-77
@@ -206,6 +219,9 @@ def main(argv=None, nsrc: int = 2):
         # burn-in cannot be taken out of them afterwards
         ap.error(f"--from-moments covers every recorded row (additional_burnin 1); "
                  f"-a {additional_burnin} needs the chain files")
+    if args.from_moments and args.astrometry:
+        ap.error("--astrometry needs the chain rows (a median is not a moment): "
+                 "drop --from-moments")
     if args.from_moments:
         with open(input_directory + "posterior_summary.json") as f:
             summ = json.load(f)
@@ -250,6 +266,60 @@ def main(argv=None, nsrc: int = 2):
            "source": "moments" if args.from_moments else ("npy" if args.npy else "csv"),
            "gr_rc_mean": float(np.mean(rc)), "gr_rc_std": float(np.std(rc)),
            "parameters": stats}
+    if args.astrometry:
+        out["astrometry"] = astrometry(args, chains, nsrc, float(np.mean(rc)),
+                                       float(np.std(rc)), say)
     with open(input_directory + "step3_summary.json", "w") as f:
         json.dump(out, f, indent=1)
     return out
+
+
+def astrometry(args, chains, nsrc, rc_mean, rc_std, say=print):
+    """apf_step3.py:211-256, :283-343, :401-450 and the two result lines of :517-546
+    (3body/apf_step3_3body.py:247-288, :315-390, :450-518, :575-613) for the chains
+    [N, M, PS] already read: the per-sample work and every reduction on the GPU
+    (astrometry.Astrometry), the header's scalars on the host.  Appends to
+    ``epoch_grand_pasep`` / ``epoch_grand_radec`` beside the image and returns what
+    ``step3_summary.json`` records.  deltaR is ``--delta-r`` (computing it needs a network
+    name resolver: not covered); the S/N and FWHM fields are ``nan`` (photometry: not
+    covered)."""
+    from . import astrometry as am, fitsio, pipeline
+    image, hdr = fitsio.getdata_header(args.image)
+    directory, _, _ = pipeline.image_paths(args.image)
+    prepost = args.prepost
+    if prepost is None:
+        try:
+            prepost = am.prepost_of(am.epoch_of(args.image))            # :149-153
+        except (ValueError, IndexError):
+            raise ValueError(f"{args.image}: the directory name does not start with the "
+                             f"epoch's year (apf_step3.py:149); give --prepost") from None
+    x_dist = y_dist = None
+    if args.distortion:
+        x_dist = np.asarray(fitsio.getdata_header(args.distortion[0])[0], dtype=np.float64)
+        y_dist = np.asarray(fitsio.getdata_header(args.distortion[1])[0], dtype=np.float64)
+        say('Correcting plate scale distortion...')                     # :217
+    else:
+        say('No distortion tables given (--distortion): no distortion correction applied')
+    say('Computing separation and position angle...')                   # :282
+    with am.Astrometry.from_header(hdr, chains.shape[1], chains.shape[0], prepost=prepost,
+                                   variant=nsrc, image_shape=image.shape, x_dist=x_dist,
+                                   y_dist=y_dist) as a:
+        a.fold_rows(chains)
+        scal = a.scalars
+        res = a.finalize(delta_r=args.delta_r)
+    say('Computing median values...')                                   # :435
+    for r in res:
+        say("r%s = " % r["pair"], r["sep_median"], "pa%s = " % r["pair"], r["pa_median"])
+    koaid = hdr.get('KOAID', '')
+    pasep = am.pasep_line(koaid, res, rc_mean, rc_std, nsrc)
+    radec = am.radec_line(koaid, res)
+    with open(directory + 'epoch_grand_pasep', 'a') as f:               # :529-533
+        f.write(pasep + "\n")
+    with open(directory + 'epoch_grand_radec', 'a') as f:               # :536-546
+        f.write(radec + "\n")
+    return {"pairs": res, "delta_r_mas": args.delta_r, "parantel": scal["parantel"],
+            "prepost": prepost, "pixscale": scal["pixscale"],
+            "rotation_angle": scal["rotation_angle"],
+            "vertical_angle_mode": scal["vertical_angle_mode"], "rotcorr": scal["rotcorr"],
+            "distortion": list(args.distortion) if args.distortion else None,
+            "pasep_line": pasep, "radec_line": radec}
