@@ -361,6 +361,50 @@ int olpe_astrom_finalize(olpe_astrom *a, double delta_r, double parantel, double
  * out[n .. 2n), n = rows x walkers, sample (row r, walker w) at r * walkers + w. */
 int olpe_astrom_samples(olpe_astrom *a, int pair, double *out);
 
+/* --- corner-plot histograms (apf_step3.py:603-643) -------------------------------------
+ * The reference ends by flattening every parameter chain into corner.corner(...,
+ * show_titles=True, plot_contours=True) (apf_step3.py:603-643; 3body/apf_step3_3body.py
+ * likewise): a 1-D histogram per column, a 2-D histogram per pair of columns and each
+ * title's 16 / 50 / 84 % quantiles.  An olpe_corner counts the data behind that figure on
+ * the device: h1 [ncols][nb1] (fine bins, which the quantile brackets are read from) and
+ * h2 [npairs][nb2][nb2] over the pairs (i, j), i < j, in lexicographic order, bin index
+ * of column i first, as np.histogram2d(x = column i, y = column j).  Counts are 64-bit and
+ * additive: they stream launch by launch without a sample store and merge across objects,
+ * ranks and checkpoints by addition; they do not depend on how the rows were split.
+ * The bin rule is NumPy's: x is in bin k of a column iff e[k] <= x < e[k+1], x equal to
+ * the last edge is in the last bin, anything else (NaN and +-inf included) is in no bin.
+ * A sample counts in h1[c] iff column c has a bin, in h2[p] iff both columns of the pair
+ * have one; n counts every sample folded.  An olpe_corner belongs to a device, not to a
+ * sampler context.  Calls on one object are not thread-safe.  Not covered: the drawing,
+ * contour levels, exact quantiles (they need a sample store). */
+typedef struct olpe_corner olpe_corner;
+/* apf_step3.py:603-643: the bin edges of every column, edges1 [ncols][nb1 + 1] for the 1-D
+ * histograms and edges2 [ncols][nb2 + 1] for the 2-D ones, each column's finite and
+ * strictly increasing (any spacing).  2 <= ncols <= 24, 2 <= nb1 <= 4096, 2 <= nb2 <= 64.
+ * Anything else is OLPE_EINVAL (naming the column) before any GPU call, as is a
+ * configuration whose smallest tile does not fit a workgroup's LDS (naming the bytes). */
+int olpe_corner_create(int device, int ncols, const double *edges1, int nb1,
+                       const double *edges2, int nb2, olpe_corner **out);
+/* Frees the object of apf_step3.py:603-643's counts (waits for its folds in flight). */
+void olpe_corner_destroy(olpe_corner *h);
+/* apf_step3.py:603-643 for the rows of ctx's last launch, read from its device chain
+ * (async on the context's stream, no host copy; ncols == PS).  Once per launch:
+ * OLPE_ESTATE if this launch was folded already; OLPE_EINVAL for a context of another
+ * device or PS. */
+int olpe_corner_fold_ctx(olpe_corner *h, olpe_ctx *ctx);
+/* apf_step3.py:603-643 for host rows [nsamples][ncols], uploaded in bounded pieces. */
+int olpe_corner_fold_rows(olpe_corner *h, const double *rows, long long nsamples);
+/* The counts so far (apf_step3.py:603-643): *n samples folded, h1 [ncols][nb1],
+ * h2 [npairs][nb2][nb2]; any of the three may be NULL.  Waits for the folds in flight. */
+int olpe_corner_get(olpe_corner *h, unsigned long long *n, unsigned long long *h1,
+                    unsigned long long *h2);
+/* Adds another object's, rank's or checkpoint's counts of the same shape
+ * (apf_step3.py:603-643 over the union of their rows). */
+int olpe_corner_add(olpe_corner *h, unsigned long long n, const unsigned long long *h1,
+                    const unsigned long long *h2);
+/* Zeroes the counts (apf_step3.py:603-643 starts over); the edges stay. */
+int olpe_corner_reset(olpe_corner *h);
+
 #ifdef __cplusplus
 }
 #endif

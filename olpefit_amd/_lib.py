@@ -31,6 +31,7 @@ _pd = C.POINTER(C.c_double)
 _pu32 = C.POINTER(C.c_uint32)
 _pu8 = C.POINTER(C.c_uint8)
 _pll = C.POINTER(C.c_longlong)
+_pu64 = C.POINTER(C.c_ulonglong)
 
 #: name -> (restype, argtypes); mirrors include/olpe.h and the test hooks of
 #: include/olpe_test.h one-to-one
@@ -93,6 +94,13 @@ SIGNATURES = {
     "olpe_astrom_rows": (_i, [_P, _pll]),
     "olpe_astrom_finalize": (_i, [_P, _d, _d, _pd]),
     "olpe_astrom_samples": (_i, [_P, _i, _pd]),
+    "olpe_corner_create": (_i, [_i, _i, _pd, _i, _pd, _i, C.POINTER(_P)]),
+    "olpe_corner_destroy": (None, [_P]),
+    "olpe_corner_fold_ctx": (_i, [_P, _P]),
+    "olpe_corner_fold_rows": (_i, [_P, _pd, _ll]),
+    "olpe_corner_get": (_i, [_P, _pu64, _pu64, _pu64]),
+    "olpe_corner_add": (_i, [_P, C.c_ulonglong, _pu64, _pu64]),
+    "olpe_corner_reset": (_i, [_P]),
     "olpe_moments_fault": (_i, [_P, _i]),
     "olpe_test_hold_handoff": (_i, [_P, _i]),
 }

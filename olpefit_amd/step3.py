@@ -208,6 +208,13 @@ def main(argv=None, nsrc: int = 2):
     ap.add_argument("--prepost", choices=("pre", "post"),
                     help="distortion epoch (default: from the year the image's directory "
                          "name starts with, apf_step3.py:149-153)")
+    ap.add_argument("--corner", action="store_true",
+                    help="the corner plot's 1-D / 2-D histograms and 16/50/84 %% quantile "
+                         "brackets of the chains (GPU); writes <frame>_corner.npz")
+    ap.add_argument("--corner-bins", type=int, default=20, metavar="N",
+                    help="bins per axis of the 2-D histograms (corner's default 20)")
+    ap.add_argument("--corner-fine-bins", type=int, default=2048, metavar="N",
+                    help="bins of the 1-D histograms the quantile brackets are read from")
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
     say = (lambda *a: None) if args.quiet else print
     ncor = int(np.int_(args.size))                                  # :76-77
@@ -221,6 +228,9 @@ def main(argv=None, nsrc: int = 2):
                  f"-a {additional_burnin} needs the chain files")
     if args.from_moments and args.astrometry:
         ap.error("--astrometry needs the chain rows (a median is not a moment): "
+                 "drop --from-moments")
+    if args.from_moments and args.corner:
+        ap.error("--corner needs the chain rows (a histogram is not a moment): "
                  "drop --from-moments")
     if args.from_moments:
         with open(input_directory + "posterior_summary.json") as f:
@@ -269,9 +279,40 @@ def main(argv=None, nsrc: int = 2):
     if args.astrometry:
         out["astrometry"] = astrometry(args, chains, nsrc, float(np.mean(rc)),
                                        float(np.std(rc)), say)
+    if args.corner:
+        out["corner"] = corner(args, chains, nsrc, input_directory, say)
     with open(input_directory + "step3_summary.json", "w") as f:
         json.dump(out, f, indent=1)
     return out
+
+
+def corner(args, chains, nsrc, input_directory, say=print):
+    """apf_step3.py:603-643 (3body/apf_step3_3body.py:680-726) without the drawing: the
+    1-D and 2-D histograms ``corner.corner`` would compute over the chains [N, M, PS]
+    already read, and its titles' quantiles as brackets, counted on the GPU
+    (corner.Corner) over corner's default range (each column's min / max).  Writes
+    ``<frame>_corner.npz`` beside the chain files and returns what ``step3_summary.json``
+    records.  The columns are the chain files' (chi^2 included); the reference's sep / pa
+    columns are not added here."""
+    from . import corner as cn
+    labels = cn.LABELS_2 if nsrc == 2 else cn.LABELS_3
+    say('Creating a corner plot...')                                    # :605
+    path = input_directory + args.image.split('/')[-1].split('.')[-3] + '_corner.npz'  # :643
+    with cn.Corner(cn.Corner.ranges_of(chains), bins=args.corner_bins,
+                   fine_bins=args.corner_fine_bins, labels=labels) as c:
+        c.fold_rows(chains)
+        counts, table = c.save(path)
+    for k, name in enumerate(labels):
+        say(f"{name:>10} " + "  ".join(
+            f"{100 * q:g}%: {e:.10g} [{lo:.10g}, {hi:.10g}]" for q, e, lo, hi in
+            zip(table["q"], table["estimate"][k], table["lo"][k], table["hi"][k])))
+    return {"file": path, "samples": counts["n"], "bins": args.corner_bins,
+            "fine_bins": args.corner_fine_bins, "labels": labels, "q": table["q"],
+            "quantiles": {name: {"lo": [float(v) for v in table["lo"][k]],
+                                 "hi": [float(v) for v in table["hi"][k]],
+                                 "estimate": [float(v) for v in table["estimate"][k]]}
+                          for k, name in enumerate(labels)},
+            "outside": [int(v) for v in counts["outside1"]]}
 
 
 def astrometry(args, chains, nsrc, rc_mean, rc_std, say=print):
