@@ -1,11 +1,13 @@
 """LAPF 3-source step 3 front end (3body/apf_step3_3body.py's arguments, read of the
 20-column chains and Gelman-Rubin statistics; with --astrometry also the separation /
-position angle / RA / Dec of b and c about a, on the GPU, and with --corner the corner
-plot's histograms and quantile brackets; see olpefit_amd/step3.py).
+position angle / RA / Dec of b and c about a, on the GPU, with --corner the corner
+plot's histograms and quantile brackets, and with --residuals the posterior's model and
+residual images; see olpefit_amd/step3.py).
 
     python 3body/apf_step3_3body.py <image> <system> -s <walkers> [-a <burn>]
         [--astrometry [--distortion X.fits Y.fits] [--delta-r MAS] [--prepost pre|post]]
         [--corner [--corner-bins N] [--corner-fine-bins N]]
+        [--residuals [--residuals-thin N] [--bkgd-mode 0|1]]
 """
 import os
 import sys

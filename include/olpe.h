@@ -405,6 +405,71 @@ int olpe_corner_add(olpe_corner *h, unsigned long long n, const unsigned long lo
 /* Zeroes the counts (apf_step3.py:603-643 starts over); the edges stay. */
 int olpe_corner_reset(olpe_corner *h);
 
+/* --- posterior model and residual images (apf_step2.py:106-124) ------------------------
+ * The picture the reference's README opens with (model_residuals_all.png: data, model,
+ * residual), over the whole ensemble: every folded sample's build_analytical_model
+ * (apf_step2.py:106-124; 3body/apf_step2_3body.py:106-125) is evaluated on the device in
+ * the EXACT operation order, whatever the context's eval mode, and folded per pixel into
+ * the shifted sums S1 = sum (M_s - R), S2 = sum (M_s - R)^2 about a pivot image R, the
+ * model of a pivot vector.  The state (counts, pivot, S1, S2, best row) is additive across
+ * folds, objects, ranks and checkpoints whose pivots are equal.  A row with a non-finite
+ * parameter (the all-NaN seed row of a chain file) contributes to nothing and is counted
+ * in n_bad.  The best sample is the usable row with the smallest chi^2 column (NaN never
+ * wins; the earliest in fold order on a tie).  No result depends on the grid, the CU
+ * count or the tile height; the same sequence of folds gives the same bits.  Calls on one
+ * object are not thread-safe.  Not covered: the drawing, a factorised (FAST) fold, a
+ * collective over the state, per-pixel chi^2 maps over all samples, photometry. */
+typedef struct olpe_resid olpe_resid;
+#define OLPE_RESID_PLANES 7
+/* olpe_resid_finalize's planes [OLPE_RESID_PLANES][n][n], D the data, err as apf_step2.py
+ * :210, chi_squared's residual as :134-137:
+ *   [0] mean of the models over the samples        [1] their np.std (ddof 0)
+ *   [2] model of the best sample                   [3] D - [2]      [4] (D - [2]) / err
+ *   [5] D - [0]                                    [6] (D - [0]) / err
+ * [3..6] are NaN at the pixels the context staged as masked.  Its scalars: */
+#define OLPE_RESID_SCALARS 8
+#define OLPE_RESID_USED 0      /* samples folded (usable) */
+#define OLPE_RESID_BAD 1       /* unusable rows met */
+#define OLPE_RESID_PIXELS 2    /* unmasked pixels */
+#define OLPE_RESID_BEST_CHI2 3 /* the best row's chi^2 column */
+#define OLPE_RESID_SUM4 4      /* sum of plane 4 squared: that chi^2 evaluated here (:134-137) */
+#define OLPE_RESID_SUM6 5      /* sum of plane 6 squared */
+#define OLPE_RESID_MAX4 6      /* max |plane 4| ... */
+#define OLPE_RESID_MAX4_AT 7   /* ... and its pixel, row * n + column */
+/* Copies ctx's staged cutout (apf_step2.py:176-210: data, 1/err, mask) device to device and
+ * takes its side, sources, bkgd_mode and device; independent of ctx afterwards.  pivot: a
+ * parameter vector (its PS - 1 parameters are read, all finite), or NULL: the first usable
+ * row folded becomes the pivot.
+ * OLPE_RESID_ROWS=8|16 picks the fold kernel's tile height (A/B; no result depends on it).
+ * OLPE_EINVAL, naming the bytes, for a frame whose partial sums per block exceed 1 GiB. */
+int olpe_resid_create(olpe_ctx *ctx, const double *pivot, olpe_resid **out);
+/* Frees the object of apf_step2.py:106-124's images (waits for its folds in flight). */
+void olpe_resid_destroy(olpe_resid *r);
+/* apf_step2.py:106-124 for rows 0, row_step, ... of walkers 0, walker_step, ... of ctx's
+ * last launch, read from its device chain in place, walker-major (async on the context's
+ * stream, no copy).  Once per launch: OLPE_ESTATE if this launch was folded already;
+ * OLPE_EINVAL for a context of another device, side, nsrc or bkgd_mode. */
+int olpe_resid_fold_ctx(olpe_resid *r, olpe_ctx *ctx, int row_step, int walker_step);
+/* apf_step2.py:106-124 for host rows [nsamples][PS], uploaded in bounded pieces. */
+int olpe_resid_fold_rows(olpe_resid *r, const double *rows, long long nsamples);
+/* The state (apf_step2.py:106-124 summed): samples used, unusable rows, pivot [PS], S1 and
+ * S2 [n*n] each, best row [PS]; any may be NULL; pivot / best are NaN while there is none.
+ * Waits for the folds in flight. */
+int olpe_resid_get(olpe_resid *r, long long *n, long long *n_bad, double *pivot, double *s1,
+                   double *s2, double *best);
+/* Adds another object's, rank's or checkpoint's state (apf_step2.py:106-124 over the union
+ * of their rows).  OLPE_EINVAL if the pivots' parameters differ in any bit, unless this
+ * object holds no sample yet: it then adopts the incoming pivot.  This object's rows count
+ * as folded first: the incoming best row wins only with a strictly smaller chi^2. */
+int olpe_resid_add(olpe_resid *r, long long n, long long n_bad, const double *pivot,
+                   const double *s1, const double *s2, const double *best);
+/* Empties the state (apf_step2.py:106-124 starts over); a pivot given at create stays. */
+int olpe_resid_reset(olpe_resid *r);
+/* The planes and scalars above (apf_step2.py:106-137 per plane) from the state, which it
+ * leaves as it is: more folds and another finalize may follow.  OLPE_ESTATE with no
+ * usable sample, or when no usable sample's chi^2 is a number. */
+int olpe_resid_finalize(olpe_resid *r, double *planes, double *scalars);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,14 @@ SIGNATURES = {
     "olpe_corner_get": (_i, [_P, _pu64, _pu64, _pu64]),
     "olpe_corner_add": (_i, [_P, C.c_ulonglong, _pu64, _pu64]),
     "olpe_corner_reset": (_i, [_P]),
+    "olpe_resid_create": (_i, [_P, _pd, C.POINTER(_P)]),
+    "olpe_resid_destroy": (None, [_P]),
+    "olpe_resid_fold_ctx": (_i, [_P, _P, _i, _i]),
+    "olpe_resid_fold_rows": (_i, [_P, _pd, _ll]),
+    "olpe_resid_get": (_i, [_P, _pll, _pll, _pd, _pd, _pd, _pd]),
+    "olpe_resid_add": (_i, [_P, _ll, _ll, _pd, _pd, _pd, _pd]),
+    "olpe_resid_reset": (_i, [_P]),
+    "olpe_resid_finalize": (_i, [_P, _pd, _pd]),
     "olpe_moments_fault": (_i, [_P, _i]),
     "olpe_test_hold_handoff": (_i, [_P, _i]),
 }

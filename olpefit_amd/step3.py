@@ -180,7 +180,9 @@ def main(argv=None, nsrc: int = 2):
     ``<frame>_apf_results/step3_summary.json``.
     ``--from-moments`` skips the chain files and uses step 2's device moments.
     ``--astrometry`` adds the separation / position-angle stages after :278 (``astrometry``
-    below); without it nothing past the statistics runs and the outputs are unchanged."""
+    below); without it nothing past the statistics runs and the outputs are unchanged.
+    ``--corner`` and ``--residuals`` add the corner plot's counts and the posterior's model
+    / residual images (``corner``, ``residuals`` below) in the same way."""
     import argparse
     import json
     import sys
@@ -215,6 +217,16 @@ def main(argv=None, nsrc: int = 2):
                     help="bins per axis of the 2-D histograms (corner's default 20)")
     ap.add_argument("--corner-fine-bins", type=int, default=2048, metavar="N",
                     help="bins of the 1-D histograms the quantile brackets are read from")
+    ap.add_argument("--residuals", action="store_true",
+                    help="posterior mean / scatter of the model and the best sample's "
+                         "residual images of the chains (GPU); writes <frame>_residuals.npz "
+                         "and four FITS files")
+    ap.add_argument("--residuals-thin", type=int, default=1, metavar="N",
+                    help="fold every N-th row after the burn-in (a full fold costs about "
+                         "what sampling the rows did)")
+    ap.add_argument("--bkgd-mode", type=int, choices=(0, 1), default=0,
+                    help="the background parameter of the models --residuals evaluates: 0 as "
+                         "step 2's default, 1 as its --fixed-bkgd")
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
     say = (lambda *a: None) if args.quiet else print
     ncor = int(np.int_(args.size))                                  # :76-77
@@ -232,6 +244,11 @@ def main(argv=None, nsrc: int = 2):
     if args.from_moments and args.corner:
         ap.error("--corner needs the chain rows (a histogram is not a moment): "
                  "drop --from-moments")
+    if args.from_moments and args.residuals:
+        ap.error("--residuals needs the chain rows (moments are not samples): "
+                 "drop --from-moments")
+    if args.residuals_thin < 1:
+        ap.error(f"--residuals-thin {args.residuals_thin}: must be >= 1")
     if args.from_moments:
         with open(input_directory + "posterior_summary.json") as f:
             summ = json.load(f)
@@ -281,6 +298,8 @@ def main(argv=None, nsrc: int = 2):
                                        float(np.std(rc)), say)
     if args.corner:
         out["corner"] = corner(args, chains, nsrc, input_directory, say)
+    if args.residuals:
+        out["residuals"] = residuals(args, chains, nsrc, input_directory, say)
     with open(input_directory + "step3_summary.json", "w") as f:
         json.dump(out, f, indent=1)
     return out
@@ -313,6 +332,30 @@ def corner(args, chains, nsrc, input_directory, say=print):
                                  "estimate": [float(v) for v in table["estimate"][k]]}
                           for k, name in enumerate(labels)},
             "outside": [int(v) for v in counts["outside1"]]}
+
+
+def residuals(args, chains, nsrc, input_directory, say=print):
+    """The picture the reference's README opens with (data, model, residual) over the
+    chains [N, M, PS] already read, without the drawing: every ``--residuals-thin``-th row's
+    ``build_analytical_model`` (apf_step2.py:106-124; 3body :106-125) folded on the GPU
+    (residuals.Residuals) on the frame as step 2 staged it (apf_step2.py:160-161,
+    :176-210).  Writes ``<frame>_residuals.npz`` and ``<frame>_model.fits``,
+    ``_meanmodel.fits``, ``_resid.fits``, ``_nresid.fits`` beside the chain files and
+    returns what ``step3_summary.json`` records."""
+    from . import fitsio, residuals as rs
+    from .core import Sampler
+    image, hdr = fitsio.getdata_header(args.image)
+    say('Building model and residual images...')
+    prefix = input_directory + args.image.split('/')[-1].split('.')[-3]
+    with Sampler(image, hdr["ITIME"], hdr["COADDS"], hdr["MULTISAM"], hdr["SAMPMODE"],
+                 nsrc=nsrc, bkgd_mode=args.bkgd_mode) as s, rs.Residuals(s) as r:
+        r.fold_rows(chains[::args.residuals_thin])
+        _, scal = r.save(prefix + "_residuals.npz")
+        files = r.write_fits(prefix)
+    for k, v in scal.items():
+        say(f"{k:>18} {v:.10g}")
+    return {"file": prefix + "_residuals.npz", "fits": files, "thin": args.residuals_thin,
+            "bkgd_mode": args.bkgd_mode, **scal}
 
 
 def astrometry(args, chains, nsrc, rc_mean, rc_std, say=print):
