@@ -1,13 +1,15 @@
 """LAPF 3-source step 3 front end (3body/apf_step3_3body.py's arguments, read of the
 20-column chains and Gelman-Rubin statistics; with --astrometry also the separation /
 position angle / RA / Dec of b and c about a, on the GPU, with --corner the corner
-plot's histograms and quantile brackets, and with --residuals the posterior's model and
-residual images; see olpefit_amd/step3.py).
+plot's histograms and quantile brackets, with --residuals the posterior's model and
+residual images, and with --autocorr the chains' autocorrelation times and effective sample
+sizes; see olpefit_amd/step3.py).
 
     python 3body/apf_step3_3body.py <image> <system> -s <walkers> [-a <burn>]
         [--astrometry [--distortion X.fits Y.fits] [--delta-r MAS] [--prepost pre|post]]
         [--corner [--corner-bins N] [--corner-fine-bins N]]
         [--residuals [--residuals-thin N] [--bkgd-mode 0|1]]
+        [--autocorr [--autocorr-max-lag N] [--autocorr-c X]]
 """
 import os
 import sys

@@ -5,12 +5,15 @@ reference does not ship, and deltaR are inputs; see olpefit_amd/step3.py); with 
 the corner plot's 1-D / 2-D histograms and quantile brackets, counted on the GPU and written
 to <frame>_corner.npz; with --residuals the posterior mean / scatter of the model and the
 best sample's residual images, folded on the GPU and written to <frame>_residuals.npz and
-four FITS files (nothing is drawn).
+four FITS files; with --autocorr an integrated autocorrelation time and effective sample size
+per parameter, the lag sums folded on the GPU and written to <frame>_autocorr.npz (nothing is
+drawn).
 
     python apf_step3.py <dir>/N2.<date>.<frame>.LDIF.fits <system> -s <walkers> [-a <burn>]
         [--astrometry [--distortion X.fits Y.fits] [--delta-r MAS] [--prepost pre|post]]
         [--corner [--corner-bins N] [--corner-fine-bins N]]
         [--residuals [--residuals-thin N] [--bkgd-mode 0|1]]
+        [--autocorr [--autocorr-max-lag N] [--autocorr-c X]]
 """
 import os
 import sys

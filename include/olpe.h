@@ -470,6 +470,54 @@ int olpe_resid_reset(olpe_resid *r);
  * usable sample, or when no usable sample's chi^2 is a number. */
 int olpe_resid_finalize(olpe_resid *r, double *planes, double *scalars);
 
+/* --- autocorrelation times of the chains (apf_step3.py:582-601) --------------------------
+ * The reference draws every walker's trace of every parameter (apf_step3.py:582-601) and
+ * additional_burnin, accept_min and the record stride are chosen from the picture.  An
+ * olpe_acf holds the numbers behind an integrated autocorrelation time per column.  A
+ * series is one walker's values of one column over one contiguous run of recorded rows
+ * x[0 .. N-1]; with the pivot p = x[0], y[t] = (x[t] - p) - mean_t(x[t] - p).  The state is,
+ * per column c and for the max_lag L given at create,
+ *     C[c][k] = sum over series  sum_{t=0}^{N-k-1} y[t] y[t+k],   k = 0 .. L
+ * (the biased lag sum, no 1 / (N - k) factor, pooled over the series; a lag k >= N adds
+ * exactly 0), and three counters: n values per column folded, series, and skipped -- a
+ * series with a non-finite value in any column is left out whole and counted (a chain
+ * file's NaN seed row).  The state is additive over launches, objects, ranks and
+ * checkpoints; tau = 2 sum_{k<=M} C[k]/C[0] - 1 and n / tau are host arithmetic on it.
+ * Every sum runs in an order fixed by the input's shape: the same call on the same input
+ * gives the same bits, whatever the device or grid.  An olpe_acf belongs to a device, not to
+ * a sampler context.  Calls on one object are not thread-safe.  Not covered: lags across
+ * launch boundaries, per-walker tau, an FFT form, a collective over the state. */
+typedef struct olpe_acf olpe_acf;
+/* apf_step3.py:582-601: 1 <= ncols <= 24; max_lag a multiple of 64 with 64 <= max_lag <=
+ * 1024.  Anything else is OLPE_EINVAL, naming the value, before any GPU call.
+ * OLPE_ACF_TILE=64..512 (a multiple of 64) sets the fold kernel's time tile (a test knob:
+ * results agree to rounding, not to the bit, across tiles). */
+int olpe_acf_create(int device, int ncols, int max_lag, olpe_acf **out);
+/* Frees the object of apf_step3.py:582-601's sums (waits for its folds in flight). */
+void olpe_acf_destroy(olpe_acf *h);
+/* apf_step3.py:582-601 for ctx's last launch: each walker's recorded rows of that launch
+ * are one series, read from the device chain in place (async on the context's stream, no
+ * host copy; ncols == PS).  Once per launch: OLPE_ESTATE if this launch was folded already;
+ * OLPE_EINVAL for a context of another device or PS. */
+int olpe_acf_fold_ctx(olpe_acf *h, olpe_ctx *ctx);
+/* apf_step3.py:582-601 for host rows: nwalkers series of nrows rows, walker-major
+ * [nwalkers][nrows][ncols] (time_major 0) or time-major [nrows][nwalkers][ncols] (1, step
+ * 3's chains), uploaded as they lie (no transposition) in pieces of whole series of at
+ * most 256 MiB.  A single series larger than that is OLPE_EINVAL, naming its bytes: fold
+ * it as shorter runs, each its own series. */
+int olpe_acf_fold_rows(olpe_acf *h, const double *rows, long long nwalkers, long long nrows,
+                       int time_major);
+/* The state so far (apf_step3.py:582-601): *n, *series, *skipped and C_out [ncols][max_lag
+ * + 1]; any may be NULL.  Waits for the folds in flight. */
+int olpe_acf_get(olpe_acf *h, unsigned long long *n, unsigned long long *series,
+                 unsigned long long *skipped, double *C_out);
+/* Adds another object's, rank's or checkpoint's state (apf_step3.py:582-601 over the union
+ * of their series).  OLPE_EINVAL, naming both, if its ncols or max_lag differ. */
+int olpe_acf_add(olpe_acf *h, int ncols, int max_lag, unsigned long long n,
+                 unsigned long long series, unsigned long long skipped, const double *C_in);
+/* Zeroes the state (apf_step3.py:582-601 starts over). */
+int olpe_acf_reset(olpe_acf *h);
+
 #ifdef __cplusplus
 }
 #endif

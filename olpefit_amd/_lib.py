@@ -109,6 +109,13 @@ SIGNATURES = {
     "olpe_resid_add": (_i, [_P, _ll, _ll, _pd, _pd, _pd, _pd]),
     "olpe_resid_reset": (_i, [_P]),
     "olpe_resid_finalize": (_i, [_P, _pd, _pd]),
+    "olpe_acf_create": (_i, [_i, _i, _i, C.POINTER(_P)]),
+    "olpe_acf_destroy": (None, [_P]),
+    "olpe_acf_fold_ctx": (_i, [_P, _P]),
+    "olpe_acf_fold_rows": (_i, [_P, _pd, _ll, _ll, _i]),
+    "olpe_acf_get": (_i, [_P, _pu64, _pu64, _pu64, _pd]),
+    "olpe_acf_add": (_i, [_P, _i, _i, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, _pd]),
+    "olpe_acf_reset": (_i, [_P]),
     "olpe_moments_fault": (_i, [_P, _i]),
     "olpe_test_hold_handoff": (_i, [_P, _i]),
 }

@@ -13,7 +13,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libolpe.so")
 SOURCES = [os.path.join(CSRC, f) for f in ("olpe.hip", "olpe_comm.hip", "olpe_moments.hip",
                                             "olpe_astrom.hip", "olpe_csv.cpp",
-                                            "olpe_corner.hip", "olpe_resid.hip")]
+                                            "olpe_corner.hip", "olpe_resid.hip",
+                                            "olpe_acf.hip")]
 DEPS = SOURCES + [os.path.join(CSRC, f) for f in ("olpe_device.h", "olpe_internal.h",
                                                  "exp_table.h", "olpe_comm_proto.h")] + [
     os.path.join(REPO, "include", h) for h in ("olpe.h", "olpe_test.h")]

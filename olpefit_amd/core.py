@@ -187,6 +187,7 @@ class Sampler:
         check(self._lib.olpe_run(self._ctx, int(n_iters), int(burn_in), int(record_stride),
                                  int(accept_min), C.byref(nrec)))
         self._nrec = int(nrec.value)
+        self._record_stride = int(record_stride)     # autocorr.Autocorr: tau in iterations
         return self._nrec
 
     def run(self, n_iters, burn_in=0, record_stride=1, accept_min=0, read_chain=True):

@@ -182,7 +182,8 @@ def main(argv=None, nsrc: int = 2):
     ``--astrometry`` adds the separation / position-angle stages after :278 (``astrometry``
     below); without it nothing past the statistics runs and the outputs are unchanged.
     ``--corner`` and ``--residuals`` add the corner plot's counts and the posterior's model
-    / residual images (``corner``, ``residuals`` below) in the same way."""
+    / residual images (``corner``, ``residuals`` below) in the same way, ``--autocorr`` the
+    chains' integrated autocorrelation times and effective sample sizes (``autocorr``)."""
     import argparse
     import json
     import sys
@@ -227,6 +228,13 @@ def main(argv=None, nsrc: int = 2):
     ap.add_argument("--bkgd-mode", type=int, choices=(0, 1), default=0,
                     help="the background parameter of the models --residuals evaluates: 0 as "
                          "step 2's default, 1 as its --fixed-bkgd")
+    ap.add_argument("--autocorr", action="store_true",
+                    help="integrated autocorrelation time and effective sample size per "
+                         "parameter of the chains (GPU); writes <frame>_autocorr.npz")
+    ap.add_argument("--autocorr-max-lag", type=int, default=512, metavar="N",
+                    help="largest lag in recorded rows (a multiple of 64, 64 to 1024)")
+    ap.add_argument("--autocorr-c", type=float, default=5.0, metavar="X",
+                    help="the window is the smallest M with M >= X tau(M) (emcee's c = 5)")
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
     say = (lambda *a: None) if args.quiet else print
     ncor = int(np.int_(args.size))                                  # :76-77
@@ -247,6 +255,12 @@ def main(argv=None, nsrc: int = 2):
     if args.from_moments and args.residuals:
         ap.error("--residuals needs the chain rows (moments are not samples): "
                  "drop --from-moments")
+    if args.from_moments and args.autocorr:
+        ap.error("--autocorr needs the chain rows (moments hold no order): "
+                 "drop --from-moments")
+    if args.autocorr and (args.autocorr_max_lag < 64 or args.autocorr_max_lag > 1024
+                          or args.autocorr_max_lag % 64):
+        ap.error(f"--autocorr-max-lag {args.autocorr_max_lag}: a multiple of 64 from 64 to 1024")
     if args.residuals_thin < 1:
         ap.error(f"--residuals-thin {args.residuals_thin}: must be >= 1")
     if args.from_moments:
@@ -300,9 +314,42 @@ def main(argv=None, nsrc: int = 2):
         out["corner"] = corner(args, chains, nsrc, input_directory, say)
     if args.residuals:
         out["residuals"] = residuals(args, chains, nsrc, input_directory, say)
+    if args.autocorr:
+        out["autocorr"] = autocorr(args, chains, nsrc, input_directory, say)
     with open(input_directory + "step3_summary.json", "w") as f:
         json.dump(out, f, indent=1)
     return out
+
+
+def autocorr(args, chains, nsrc, input_directory, say=print):
+    """The numbers behind the reference's chain plot (apf_step3.py:582-601;
+    3body/apf_step3_3body.py likewise), which is read by eye: an integrated autocorrelation
+    time and an effective sample size per column of the chains [N, M, PS] already read, each
+    walker's file one series, the lag sums folded on the GPU (autocorr.Autocorr) from the
+    rows as they lie (time-major).  Writes ``<frame>_autocorr.npz`` beside the chain files
+    and returns what ``step3_summary.json`` records.  tau is in recorded rows."""
+    from . import autocorr as ac
+    labels = NAMES_2 if nsrc == 2 else NAMES_3
+    say('Computing autocorrelation times...')
+    path = input_directory + args.image.split('/')[-1].split('.')[-3] + '_autocorr.npz'
+    with ac.Autocorr(chains.shape[2], args.autocorr_max_lag, labels=labels) as a:
+        a.fold_rows(chains, time_major=True)
+        st, res = a.save(path, c=args.autocorr_c)
+    for line in ac.table_lines(res):
+        say(line)
+    say("Smallest effective sample size:", res["min_ess"])
+
+    def num(v):                                   # JSON has no NaN
+        return float(v) if np.isfinite(v) else None
+    return {"file": path, "max_lag": args.autocorr_max_lag, "c": args.autocorr_c,
+            "tol": res["tol"], "n": st["n"], "series": st["series"], "skipped": st["skipped"],
+            "min_ess": num(res["min_ess"]),
+            "columns": {name: {"tau": num(res["tau"][k]), "window": int(res["window"][k]),
+                               "windowed": bool(res["windowed"][k]),
+                               "reliable": bool(res["reliable"][k]), "ess": num(res["ess"][k]),
+                               "suggested_stride": int(res["suggested_stride"][k]),
+                               "note": res["notes"][k]}
+                        for k, name in enumerate(labels)}}
 
 
 def corner(args, chains, nsrc, input_directory, say=print):
