@@ -19,6 +19,7 @@ import math
 import numpy as np
 
 from . import _lib
+from ._handle import Handle, _pd
 from ._lib import check
 
 OUT_LEN = 16
@@ -110,9 +111,11 @@ def radec_line(koaid, results) -> str:
     return " , ".join(f)
 
 
-class Astrometry:
+class Astrometry(Handle):
     """One ``olpe_astrom``: the (sep, pa) samples of up to ``row_capacity`` rows of
     ``walkers`` walkers on one GPU."""
+
+    _destroy = "olpe_astrom_destroy"
 
     def __init__(self, walkers: int, row_capacity: int, *, variant: int = 2, ps: int | None = None,
                  pixscale: float, rotation_angle: float, rotcorr: float = 0.0,
@@ -140,12 +143,11 @@ class Astrometry:
         self.W, self.capacity = int(walkers), int(row_capacity)
         self.parantel = float(parantel)
         self._lib = lib
-        self._h = None
         h = C.c_void_p()
         check(lib.olpe_astrom_create(
             int(device), variant, self.ps, cols.ctypes.data_as(C.POINTER(C.c_int)), self.npairs,
-            None if xd is None else xd.ctypes.data_as(_lib._pd),
-            None if yd is None else yd.ctypes.data_as(_lib._pd), ny, nx, int(xdiff), int(ydiff),
+            None if xd is None else _pd(xd), None if yd is None else _pd(yd), ny, nx,
+            int(xdiff), int(ydiff),
             float(pixscale), float(rotation_angle), float(rotcorr), int(bool(use_rotcorr)),
             self.W, self.capacity, C.byref(h)))
         self._h = h
@@ -174,23 +176,6 @@ class Astrometry:
         a.scalars = s
         return a
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.olpe_astrom_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
     @property
     def rows(self) -> int:
         n = C.c_longlong(0)
@@ -207,14 +192,13 @@ class Astrometry:
         c = np.ascontiguousarray(chains, dtype=np.float64)
         if c.ndim != 3 or c.shape[1] != self.W or c.shape[2] != self.ps:
             raise ValueError(f"rows of shape {c.shape}, expected (rows, {self.W}, {self.ps})")
-        check(self._lib.olpe_astrom_fold_rows(self._h, c.ctypes.data_as(_lib._pd), c.shape[0]))
+        check(self._lib.olpe_astrom_fold_rows(self._h, _pd(c), c.shape[0]))
 
     def finalize(self, delta_r: float = 0.0, parantel: float | None = None):
         """The reference's summary per pair (a list of dicts, one per pair)."""
         out = np.zeros((self.npairs, OUT_LEN))
         par = self.parantel if parantel is None else float(parantel)
-        check(self._lib.olpe_astrom_finalize(self._h, float(delta_r), par,
-                                             out.ctypes.data_as(_lib._pd)))
+        check(self._lib.olpe_astrom_finalize(self._h, float(delta_r), par, _pd(out)))
         res = []
         for p in range(self.npairs):
             o = out[p]
@@ -234,5 +218,5 @@ class Astrometry:
         """After finalize: the device's (sep_corrected, pa_angle), each [rows, walkers]."""
         rows = self.rows
         out = np.empty((2, rows, self.W))
-        check(self._lib.olpe_astrom_samples(self._h, int(pair), out.ctypes.data_as(_lib._pd)))
+        check(self._lib.olpe_astrom_samples(self._h, int(pair), _pd(out)))
         return out[0], out[1]

@@ -24,13 +24,10 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._handle import Handle, _pd, _u64, load_npz  # noqa: F401  (load_npz: Autocorr.save's reader)
 from ._lib import check
 
 MAX_COLS, MIN_LAG, MAX_LAG = 24, 64, 1024
-
-
-def _u64(a):
-    return a.ctypes.data_as(_lib._pu64)
 
 
 def integrated_time(C, n, series, c: float = 5.0, tol: float = 50.0):
@@ -91,9 +88,11 @@ def integrated_time(C, n, series, c: float = 5.0, tol: float = 50.0):
             "n": n, "series": series, "c": float(c), "tol": float(tol)}
 
 
-class Autocorr:
+class Autocorr(Handle):
     """One ``olpe_acf``: the pooled lag sums of [..., ncols] chains on one GPU.
     ``max_lag`` is a multiple of 64 from 64 to 1024; 1 <= ncols <= 24."""
+
+    _destroy = "olpe_acf_destroy"
 
     def __init__(self, ncols: int, max_lag: int = 512, labels=None, device: int = 0):
         self.ncols, self.max_lag = int(ncols), int(max_lag)
@@ -106,28 +105,9 @@ class Autocorr:
         self.record_stride = None
         self._strides = set()
         self._lib = _lib.load()
-        self._h = None
         h = C.c_void_p()
         check(self._lib.olpe_acf_create(int(device), self.ncols, self.max_lag, C.byref(h)))
         self._h = h
-
-    # -- lifetime -----------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.olpe_acf_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     # -- folding ------------------------------------------------------------------
     def _stride_seen(self, s):
@@ -151,7 +131,7 @@ class Autocorr:
             raise ValueError(f"rows of shape {r.shape}, expected [walkers][rows][{self.ncols}] "
                              f"(or [rows][walkers][{self.ncols}] with time_major)")
         nw, nr = (r.shape[1], r.shape[0]) if time_major else (r.shape[0], r.shape[1])
-        check(self._lib.olpe_acf_fold_rows(self._h, r.ctypes.data_as(_lib._pd), nw, nr,
+        check(self._lib.olpe_acf_fold_rows(self._h, _pd(r), nw, nr,
                                            int(bool(time_major))))
         self._stride_seen(0)
 
@@ -160,7 +140,7 @@ class Autocorr:
         n, ser, sk = C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0)
         Cm = np.zeros((self.ncols, self.max_lag + 1))
         check(self._lib.olpe_acf_get(self._h, C.byref(n), C.byref(ser), C.byref(sk),
-                                     Cm.ctypes.data_as(_lib._pd)))
+                                     _pd(Cm)))
         return {"ncols": self.ncols, "max_lag": self.max_lag, "n": int(n.value),
                 "series": int(ser.value), "skipped": int(sk.value), "C": Cm}
 
@@ -172,7 +152,7 @@ class Autocorr:
             raise ValueError(f"C of shape {Cm.shape}")
         check(self._lib.olpe_acf_add(self._h, int(Cm.shape[0]), int(Cm.shape[1]) - 1,
                                      int(state["n"]), int(state["series"]),
-                                     int(state["skipped"]), Cm.ctypes.data_as(_lib._pd)))
+                                     int(state["skipped"]), _pd(Cm)))
 
     def reset(self):
         check(self._lib.olpe_acf_reset(self._h))
@@ -212,12 +192,6 @@ def save_npz(path, state, res):
                  notes=np.asarray(res["notes"], dtype="U"), c=np.float64(res["c"]),
                  tol=np.float64(res["tol"]), min_ess=np.float64(res["min_ess"]),
                  record_stride=np.int64(res["record_stride"] or 0))
-
-
-def load_npz(path):
-    """What ``Autocorr.save`` wrote, as a dict of arrays."""
-    with np.load(path, allow_pickle=False) as z:
-        return {k: z[k] for k in z.files}
 
 
 def table_lines(res):

@@ -16,7 +16,8 @@ SOURCES = [os.path.join(CSRC, f) for f in ("olpe.hip", "olpe_comm.hip", "olpe_mo
                                             "olpe_corner.hip", "olpe_resid.hip",
                                             "olpe_acf.hip")]
 DEPS = SOURCES + [os.path.join(CSRC, f) for f in ("olpe_device.h", "olpe_internal.h",
-                                                 "exp_table.h", "olpe_comm_proto.h")] + [
+                                                 "olpe_fold.h", "exp_table.h",
+                                                 "olpe_comm_proto.h")] + [
     os.path.join(REPO, "include", h) for h in ("olpe.h", "olpe_test.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-shared", "-std=c++17",

@@ -20,6 +20,7 @@ from fractions import Fraction
 import numpy as np
 
 from . import _lib
+from ._handle import Handle, _pd, _u64, load_npz  # noqa: F401  (load_npz: Corner.save's reader)
 from ._lib import check
 
 MAX_COLS, MAX_BINS, MAX_FINE_BINS = 24, 64, 4096
@@ -29,10 +30,6 @@ LABELS_2 = ["xcs", "ycs", "xcc", "ycc", "dx", "dy", "amps", "ampc", "ampratio", 
 LABELS_3 = ["xca", "yca", "xcb", "ycb", "xcc", "ycc", "dx", "dy", "ampa", "ampb", "ampc",
             "ampratio", "bkgd", "sigmax", "sigmay", "sigmax2", "sigmay2", "theta", "theta2",
             "chisquared"]
-
-
-def _u64(a):
-    return a.ctypes.data_as(_lib._pu64)
 
 
 def pairs_of(ncols: int):
@@ -117,11 +114,13 @@ def quantile_table(edges, h1, n, q=(0.16, 0.5, 0.84)):
     return {"q": q, "lo": lo, "hi": hi, "estimate": est, "notes": notes}
 
 
-class Corner:
+class Corner(Handle):
     """One ``olpe_corner``: the corner plot's 1-D and 2-D counts of [..., ncols] rows on
     one GPU.  ``ranges`` [ncols][2] = (lo, hi) per column; both edge sets are
     ``np.linspace(lo, hi, n + 1)`` (``bins`` per axis of the 2-D histograms, corner's
     default 20; ``fine_bins`` for the 1-D ones the quantiles are read from)."""
+
+    _destroy = "olpe_corner_destroy"
 
     def __init__(self, ranges, *, bins: int = 20, fine_bins: int = 2048, labels=None,
                  device: int = 0, edges=None, fine_edges=None):
@@ -145,11 +144,10 @@ class Corner:
         if len(self.labels) != self.ncols:
             raise ValueError(f"{len(self.labels)} labels for {self.ncols} columns")
         self._lib = _lib.load()
-        self._h = None
         h = C.c_void_p()
-        check(self._lib.olpe_corner_create(int(device), self.ncols, self.fine_edges.ctypes.data_as(
-            _lib._pd), self.fine_bins, self.edges.ctypes.data_as(_lib._pd), self.bins,
-            C.byref(h)))
+        check(self._lib.olpe_corner_create(int(device), self.ncols, _pd(self.fine_edges),
+                                            self.fine_bins, _pd(self.edges), self.bins,
+                                            C.byref(h)))
         self._h = h
 
     # -- ranges -------------------------------------------------------------------
@@ -181,24 +179,6 @@ class Corner:
         half = np.where(half > 0, half, 0.5)
         return np.stack([mean - half, mean + half], axis=1)
 
-    # -- lifetime -----------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.olpe_corner_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
     # -- folding ------------------------------------------------------------------
     def fold(self, sampler):
         """Fold the rows of the sampler's last launch from its device chain (once per
@@ -212,7 +192,7 @@ class Corner:
         if r.ndim < 1 or r.shape[-1] != self.ncols:
             raise ValueError(f"rows of shape {r.shape}, expected [..., {self.ncols}]")
         n = r.size // self.ncols
-        check(self._lib.olpe_corner_fold_rows(self._h, r.ctypes.data_as(_lib._pd), n))
+        check(self._lib.olpe_corner_fold_rows(self._h, _pd(r), n))
 
     def counts(self):
         """``{"n", "h1" [C][fine_bins], "h2" [npairs][bins][bins], "outside1" [C],
@@ -264,9 +244,3 @@ def save_npz(path, labels, edges, fine_edges, counts, table):
                  pairs=np.asarray(pairs_of(len(labels)), dtype=np.int32),
                  q=np.asarray(table["q"]), q_lo=table["lo"], q_hi=table["hi"],
                  q_estimate=table["estimate"], q_notes=np.asarray(table["notes"], dtype="U"))
-
-
-def load_npz(path):
-    """What ``Corner.save`` wrote, as a dict of arrays."""
-    with np.load(path, allow_pickle=False) as z:
-        return {k: z[k] for k in z.files}

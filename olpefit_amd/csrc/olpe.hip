@@ -845,13 +845,6 @@ int set_err(int code, const char *fmt, ...) {
 
 }  // namespace olpe
 
-#define HIPCHK(expr)                                                                \
-  do {                                                                              \
-    hipError_t e_ = (expr);                                                         \
-    if (e_ != hipSuccess)                                                           \
-      return set_err(OLPE_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_));     \
-  } while (0)
-
 namespace {
 
 template <class T> int dev_alloc(T **p, size_t count) {

@@ -40,19 +40,14 @@
 #include <vector>
 
 #include "../../include/olpe.h"
+#include "olpe_fold.h"
 #include "olpe_internal.h"
 
-using olpe::set_err;
+using namespace olpe;
 
-struct olpe_acf {
-  int device = 0;
+struct olpe_acf : FoldBase {
   int ncols = 0, L = 0;
   int tile_knob = 0;                  // OLPE_ACF_TILE (0 = chosen per fold)
-  hipStream_t stream = nullptr;
-  hipEvent_t ev = nullptr;            // the last fold on a sampler's stream
-  bool ev_pending = false;
-  const olpe_ctx *last_ctx = nullptr;
-  long long last_launch = 0;
   double *d_C = nullptr;              // [ncols][L + 1]
   unsigned long long *d_cnt = nullptr;  // {n, series, skipped}
   // per-fold work buffers, grown on demand
@@ -67,13 +62,6 @@ struct olpe_acf {
 };
 
 namespace {
-
-#define HIPCHK(expr)                                                                    \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess)                                                               \
-      return set_err(OLPE_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_));         \
-  } while (0)
 
 constexpr int kMaxCols = 24, kMinLag = 64, kMaxLag = 1024;
 constexpr int kR = 8, kU = 8;                      // lags per lane, times per block
@@ -324,26 +312,6 @@ __global__ __launch_bounds__(256) void acf_reduce0_kernel(
   }
 }
 
-int alloc(void **p, size_t bytes, const char *what) {
-  if (hipMalloc(p, bytes) != hipSuccess) {
-    *p = nullptr;
-    (void)hipGetLastError();
-    return set_err(OLPE_ENOMEM, "hipMalloc(%zu bytes) for %s", bytes, what);
-  }
-  return OLPE_OK;
-}
-
-// a buffer of at least `bytes` (nothing of this object is in flight when it grows)
-int grow(void **p, size_t *cap, size_t bytes, const char *what) {
-  if (*cap >= bytes) return OLPE_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  int rc = alloc(p, bytes, what);
-  if (!rc) *cap = bytes;
-  return rc;
-}
-
 // The time tile, the column groups and the lanes' roles for series of N rows.
 // Among the tiles (multiples of 64 rows up to 512) whose columns fit the LDS budget, the
 // one that stages the fewest rows per row of work, (T + L) / T x groups; the larger on a tie.
@@ -420,16 +388,6 @@ int launch_fold(olpe_acf *h, hipStream_t stream, const double *d_x, long long ws
   return OLPE_OK;
 }
 
-// everything this object has in flight is done when this returns
-int drain(olpe_acf *h) {
-  if (h->ev_pending) {
-    HIPCHK(hipEventSynchronize(h->ev));
-    h->ev_pending = false;
-  }
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return OLPE_OK;
-}
-
 // the work buffers of a fold of nser series (drained first: they may be replaced)
 int reserve(olpe_acf *h, long long nser) {
   const size_t C = (size_t)h->ncols;
@@ -460,7 +418,6 @@ extern "C" {
 int olpe_acf_create(int device, int ncols, int max_lag, olpe_acf **out) {
   if (!out) return set_err(OLPE_EINVAL, "NULL out");
   *out = nullptr;
-  if (device < 0) return set_err(OLPE_EINVAL, "device %d (there is no CPU path)", device);
   if (ncols < 1 || ncols > kMaxCols)
     return set_err(OLPE_EINVAL, "ncols %d: 1 to %d columns", ncols, kMaxCols);
   if (max_lag < kMinLag || max_lag > kMaxLag || max_lag % 64)
@@ -478,24 +435,16 @@ int olpe_acf_create(int device, int ncols, int max_lag, olpe_acf **out) {
                      "budget of %zu bytes", t, v, max_lag, kLdsBudget);
     knob = (int)v;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
-    (void)hipGetLastError();
-    return set_err(OLPE_EHIP, "no HIP device %d (%d visible)", device, ndev);
-  }
-  HIPCHK(hipSetDevice(device));
+  int rc;
+  if ((rc = open_device(device))) return rc;
   olpe_acf *h = new olpe_acf;
-  h->device = device;
   h->ncols = ncols;
   h->L = max_lag;
   h->tile_knob = knob;
   const size_t cb = (size_t)ncols * (max_lag + 1) * 8;
   // one slot array serves every fold: [kMaxSlots][ncols][L]
   const size_t pb = (size_t)kMaxSlots * ncols * max_lag * 8;
-  int rc = OLPE_OK;
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev, hipEventDisableTiming) != hipSuccess)
-    rc = set_err(OLPE_EHIP, "stream / event creation failed");
+  rc = fold_open(h, device);
   if (!rc && (hipFuncSetAttribute((const void *)acf_fold_kernel<1>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)kLdsBudget) != hipSuccess ||
@@ -519,14 +468,7 @@ int olpe_acf_create(int device, int ncols, int max_lag, olpe_acf **out) {
 
 void olpe_acf_destroy(olpe_acf *h) {
   if (!h) return;
-  (void)hipSetDevice(h->device);
-  if (h->ev_pending) (void)hipEventSynchronize(h->ev);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  void *bufs[] = {h->d_C, h->d_cnt, h->d_stat, h->d_c0, h->d_use, h->d_part, h->d_stage};
-  for (void *b : bufs)
-    if (b) (void)hipFree(b);
-  if (h->ev) (void)hipEventDestroy(h->ev);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
+  fold_close(h, {h->d_C, h->d_cnt, h->d_stat, h->d_c0, h->d_use, h->d_part, h->d_stage});
   delete h;
 }
 
@@ -535,28 +477,17 @@ int olpe_acf_fold_ctx(olpe_acf *h, olpe_ctx *c) {
   if (c->device != h->device || c->ps != h->ncols)
     return set_err(OLPE_EINVAL, "context of device %d, PS %d; autocorrelation of device %d, %d "
                    "columns", c->device, c->ps, h->device, h->ncols);
-  if (!c->d_state || !c->launches) return set_err(OLPE_ESTATE, "no sampler launch yet");
-  if (h->last_ctx == c && h->last_launch == c->launches)
-    return set_err(OLPE_ESTATE, "the last launch's rows are already folded");
-  HIPCHK(hipSetDevice(h->device));
   int rc;
+  if ((rc = fold_check(h, c))) return rc;
+  HIPCHK(hipSetDevice(h->device));
   const long long N = c->chain_rows;
   if (N > 0 && (rc = reserve(h, c->W))) return rc;
-  h->last_ctx = c;
-  h->last_launch = c->launches;
+  fold_mark(h, c);
   if (N == 0 || c->W == 0) return OLPE_OK;
-  // on the sampler's stream, behind the launch and whatever this object has in flight
-  if (h->ev_pending) {
-    HIPCHK(hipStreamWaitEvent(h->stream, h->ev, 0));
-    h->ev_pending = false;
-  }
-  HIPCHK(hipEventRecord(h->ev, h->stream));
-  HIPCHK(hipStreamWaitEvent(c->stream, h->ev, 0));
+  if ((rc = fold_enter(h, c))) return rc;
   // [W][nrec][PS]: a walker's rows of this launch are one series
   if ((rc = launch_fold(h, c->stream, c->d_chain, N * c->ps, c->ps, c->W, N))) return rc;
-  HIPCHK(hipEventRecord(h->ev, c->stream));
-  h->ev_pending = true;
-  return OLPE_OK;
+  return fold_leave(h, c);
 }
 
 int olpe_acf_fold_rows(olpe_acf *h, const double *rows, long long nwalkers, long long nrows,
@@ -646,8 +577,7 @@ int olpe_acf_reset(olpe_acf *h) {
   if ((rc = drain(h))) return rc;
   HIPCHK(hipMemset(h->d_C, 0, (size_t)h->ncols * (h->L + 1) * 8));
   HIPCHK(hipMemset(h->d_cnt, 0, 3 * 8));
-  h->last_ctx = nullptr;
-  h->last_launch = 0;
+  fold_forget(h);
   return OLPE_OK;
 }
 

@@ -27,12 +27,12 @@
 #include <vector>
 
 #include "../../include/olpe.h"
+#include "olpe_fold.h"
 #include "olpe_internal.h"
 
-using olpe::set_err;
+using namespace olpe;
 
-struct olpe_astrom {
-  int device = 0;
+struct olpe_astrom : FoldBase {
   int variant = 2;
   int ps = 17;
   int npairs = 1;
@@ -44,11 +44,6 @@ struct olpe_astrom {
   long long W = 0, cap = 0;   // walkers, row capacity per walker
   long long rows = 0;         // rows folded per walker
   bool finalized = false;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev = nullptr;    // the last fold on a sampler's stream
-  bool ev_pending = false;
-  const olpe_ctx *last_ctx = nullptr;
-  long long last_launch = 0;
   double *d_xd = nullptr, *d_yd = nullptr;
   double *d_store = nullptr;  // [npairs][2][cap * W]
   double *d_pos = nullptr;    // [cap * G][npairs][4] block sums of the positions
@@ -61,13 +56,6 @@ struct olpe_astrom {
 };
 
 namespace {
-
-#define HIPCHK(expr)                                                                    \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess)                                                               \
-      return set_err(OLPE_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_));         \
-  } while (0)
 
 constexpr int kThreads = 256;
 constexpr int kPer = 16;                       // samples per thread of a reduction block
@@ -427,15 +415,6 @@ int median(olpe_astrom *a, const double *x, long long n, unsigned long long kmin
   return OLPE_OK;
 }
 
-int alloc(void **p, size_t bytes, const char *what) {
-  if (hipMalloc(p, bytes) != hipSuccess) {
-    *p = nullptr;
-    (void)hipGetLastError();
-    return set_err(OLPE_ENOMEM, "hipMalloc(%zu bytes) for %s", bytes, what);
-  }
-  return OLPE_OK;
-}
-
 FoldCfg fold_cfg(const olpe_astrom *a) {
   FoldCfg f;
   f.variant = a->variant;
@@ -467,14 +446,6 @@ int launch_fold(olpe_astrom *a, hipStream_t stream, const double *src, long long
   return OLPE_OK;
 }
 
-int wait_pending(olpe_astrom *a) {
-  if (a->ev_pending) {
-    HIPCHK(hipStreamWaitEvent(a->stream, a->ev, 0));
-    a->ev_pending = false;
-  }
-  return OLPE_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -486,7 +457,6 @@ int olpe_astrom_create(int device, int variant, int ps, const int *pair_cols, in
                        olpe_astrom **out) {
   if (!out) return set_err(OLPE_EINVAL, "NULL out");
   *out = nullptr;
-  if (device < 0) return set_err(OLPE_EINVAL, "device %d (there is no CPU path)", device);
   if (variant != 2 && variant != 3) return set_err(OLPE_EINVAL, "variant %d: 2 or 3", variant);
   if (npairs != (variant == 2 ? 1 : 2))
     return set_err(OLPE_EINVAL, "variant %d has %d pair(s), not %d", variant, variant - 1, npairs);
@@ -503,14 +473,9 @@ int olpe_astrom_create(int device, int variant, int ps, const int *pair_cols, in
   if (walkers < 1 || row_cap < 1 || walkers > (65535ll * kThreads) || row_cap > 0x7fffffffll ||
       walkers > (1ll << 40) / row_cap)
     return set_err(OLPE_EINVAL, "walkers %lld x row capacity %lld", walkers, row_cap);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
-    (void)hipGetLastError();
-    return set_err(OLPE_EHIP, "no HIP device %d (%d visible)", device, ndev);
-  }
-  HIPCHK(hipSetDevice(device));
+  int rc;
+  if ((rc = open_device(device))) return rc;
   olpe_astrom *a = new olpe_astrom;
-  a->device = device;
   a->variant = variant;
   a->ps = ps;
   a->npairs = npairs;
@@ -530,10 +495,7 @@ int olpe_astrom_create(int device, int variant, int ps, const int *pair_cols, in
   const size_t N = (size_t)walkers * row_cap;
   const size_t nblk = (N + kChunk - 1) / kChunk;
   const size_t npos = (size_t)row_cap * groups(a) * npairs * 4;
-  int rc = OLPE_OK;
-  if (hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&a->ev, hipEventDisableTiming) != hipSuccess)
-    rc = set_err(OLPE_EHIP, "stream / event creation failed");
+  rc = fold_open(a, device);
   if (!rc) rc = alloc((void **)&a->d_store, N * 2 * npairs * 8, "the astrometry sample store");
   if (!rc) rc = alloc((void **)&a->d_pos, npos * 8, "the position partials");
   if (!rc) rc = alloc((void **)&a->d_part, std::max<size_t>(nblk, npos / kChunk + 1) * 4 * 8,
@@ -561,15 +523,8 @@ int olpe_astrom_create(int device, int variant, int ps, const int *pair_cols, in
 
 void olpe_astrom_destroy(olpe_astrom *a) {
   if (!a) return;
-  (void)hipSetDevice(a->device);
-  if (a->stream) (void)hipStreamSynchronize(a->stream);
-  if (a->ev_pending) (void)hipEventSynchronize(a->ev);
-  void *bufs[] = {a->d_xd, a->d_yd, a->d_store, a->d_pos, a->d_part,
-                  a->d_out, a->d_words, a->d_hist, a->d_stage};
-  for (void *b : bufs)
-    if (b) (void)hipFree(b);
-  if (a->ev) (void)hipEventDestroy(a->ev);
-  if (a->stream) (void)hipStreamDestroy(a->stream);
+  fold_close(a, {a->d_xd, a->d_yd, a->d_store, a->d_pos, a->d_part, a->d_out, a->d_words,
+                 a->d_hist, a->d_stage});
   delete a;
 }
 
@@ -579,26 +534,19 @@ int olpe_astrom_fold_ctx(olpe_astrom *a, olpe_ctx *c) {
     return set_err(OLPE_EINVAL, "context of device %d, %d walkers, PS %d; astrometry of device "
                    "%d, %lld walkers, PS %d", c->device, c->W, c->ps, a->device, a->W, a->ps);
   if (a->finalized) return set_err(OLPE_ESTATE, "fold after finalize");
-  if (!c->d_state || !c->launches) return set_err(OLPE_ESTATE, "no sampler launch yet");
-  if (a->last_ctx == c && a->last_launch == c->launches)
-    return set_err(OLPE_ESTATE, "the last launch's rows are already folded");
+  int rc;
+  if ((rc = fold_check(a, c))) return rc;
   const long long nrec = c->chain_rows;
   if (a->rows + nrec > a->cap)
     return set_err(OLPE_ESTATE, "sample store full: %lld + %lld rows per walker, capacity %lld",
                    a->rows, nrec, a->cap);
   HIPCHK(hipSetDevice(a->device));
-  int rc;
-  if ((rc = wait_pending(a))) return rc;
-  a->last_ctx = c;
-  a->last_launch = c->launches;
+  fold_mark(a, c);
   if (nrec == 0) return OLPE_OK;
-  // on the sampler's stream, behind the launch and whatever this object has in flight
-  HIPCHK(hipEventRecord(a->ev, a->stream));
-  HIPCHK(hipStreamWaitEvent(c->stream, a->ev, 0));
+  if ((rc = fold_enter(a, c))) return rc;
   if ((rc = launch_fold(a, c->stream, c->d_chain, nrec * c->ps, c->ps, fold_cfg(a), nrec)))
     return rc;
-  HIPCHK(hipEventRecord(a->ev, c->stream));
-  a->ev_pending = true;
+  if ((rc = fold_leave(a, c))) return rc;
   a->rows += nrec;
   return OLPE_OK;
 }
@@ -625,13 +573,9 @@ int olpe_astrom_fold_rows(olpe_astrom *a, const double *rows, long long nrows) {
     }
   const long long per_row = a->W * nu;
   const long long chunk = std::max(1ll, std::min(nrows, (long long)(1 << 23) / per_row));
-  if ((size_t)(chunk * per_row) > a->stage_cap) {
-    if (a->d_stage) (void)hipFree(a->d_stage);
-    a->stage_cap = 0;
-    if ((rc = alloc((void **)&a->d_stage, (size_t)(chunk * per_row) * 8, "the row upload")))
-      return rc;
-    a->stage_cap = (size_t)(chunk * per_row);
-  }
+  if ((rc = grow((void **)&a->d_stage, &a->stage_cap, (size_t)(chunk * per_row) * 8,
+                 "the row upload")))
+    return rc;
   std::vector<double> pack((size_t)(chunk * per_row));
   for (long long r0 = 0; r0 < nrows; r0 += chunk) {
     const long long nr = std::min(chunk, nrows - r0);

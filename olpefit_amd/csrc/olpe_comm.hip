@@ -42,13 +42,6 @@ namespace proto = olpe::proto;
 
 namespace {
 
-#define HIPCHK(expr)                                                                    \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess)                                                               \
-      return set_err(OLPE_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_));         \
-  } while (0)
-
 // the context's comm buffer (olpe_comm_setup): check words | i64 poison | f64 poison
 constexpr size_t kPoisonI64Off = 16, kPoisonF64Off = 32;
 static_assert(proto::kCheckWords <= 16, "check words fit their slot");

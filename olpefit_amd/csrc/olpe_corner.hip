@@ -31,12 +31,12 @@
 #include <vector>
 
 #include "../../include/olpe.h"
+#include "olpe_fold.h"
 #include "olpe_internal.h"
 
-using olpe::set_err;
+using namespace olpe;
 
-struct olpe_corner {
-  int device = 0;
+struct olpe_corner : FoldBase {
   int ncols = 0, nb1 = 0, nb2 = 0, npairs = 0;
   int cpt = 0, ntiles1 = 0;     // columns per 1-D tile, tiles
   int ppt = 0, ntiles2 = 0;     // pairs per 2-D tile, tiles
@@ -44,11 +44,6 @@ struct olpe_corner {
   int form = 1;                 // 2-D increments: 0 = a lane per sample, 1 = a lane per pair
   unsigned long long n = 0;     // samples folded
   size_t ncount = 0;            // ncols * nb1 + npairs * nb2 * nb2
-  hipStream_t stream = nullptr;
-  hipEvent_t ev = nullptr;      // the last fold on a sampler's stream
-  bool ev_pending = false;
-  const olpe_ctx *last_ctx = nullptr;
-  long long last_launch = 0;
   double *d_e1 = nullptr, *d_e2 = nullptr;   // [ncols][nb1 + 1], [ncols][nb2 + 1]
   double2 *d_g1 = nullptr, *d_g2 = nullptr;  // per column {first edge, bins per unit}
   unsigned short *d_tab = nullptr;           // [npairs] (i << 8) | j
@@ -57,13 +52,6 @@ struct olpe_corner {
 };
 
 namespace {
-
-#define HIPCHK(expr)                                                                    \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess)                                                               \
-      return set_err(OLPE_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_));         \
-  } while (0)
 
 constexpr int kThreads = 512;
 constexpr int kMaxCols = 24, kMaxNb1 = 4096, kMaxNb2 = 64;
@@ -244,15 +232,6 @@ __global__ __launch_bounds__(kThreads) void corner_fold2_kernel(
   }
 }
 
-int alloc(void **p, size_t bytes, const char *what) {
-  if (hipMalloc(p, bytes) != hipSuccess) {
-    *p = nullptr;
-    (void)hipGetLastError();
-    return set_err(OLPE_ENOMEM, "hipMalloc(%zu bytes) for %s", bytes, what);
-  }
-  return OLPE_OK;
-}
-
 size_t lds2_bytes(int ncols, int nb2, int ppt) {
   return (size_t)ncols * (nb2 + 1) * 8 + (size_t)ncols * 16 + (size_t)ppt * pair_stride(nb2) * 4 + (size_t)((ppt + 3) & ~3) * 2 +
          (size_t)ncols * kBinStride;
@@ -311,16 +290,6 @@ int launch_fold(olpe_corner *h, hipStream_t stream, const double *d_rows, long l
   return OLPE_OK;
 }
 
-// everything this object has in flight is done when this returns
-int drain(olpe_corner *h) {
-  if (h->ev_pending) {
-    HIPCHK(hipEventSynchronize(h->ev));
-    h->ev_pending = false;
-  }
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return OLPE_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -329,7 +298,6 @@ int olpe_corner_create(int device, int ncols, const double *edges1, int nb1,
                        const double *edges2, int nb2, olpe_corner **out) {
   if (!out) return set_err(OLPE_EINVAL, "NULL out");
   *out = nullptr;
-  if (device < 0) return set_err(OLPE_EINVAL, "device %d (there is no CPU path)", device);
   if (ncols < 2 || ncols > kMaxCols)
     return set_err(OLPE_EINVAL, "ncols %d: 2 to %d columns", ncols, kMaxCols);
   if (nb1 < 2 || nb1 > kMaxNb1)
@@ -353,14 +321,8 @@ int olpe_corner_create(int device, int ncols, const double *edges1, int nb1,
     else if (!strcmp(f, "pair")) form = 1;
     else return set_err(OLPE_EINVAL, "OLPE_CORNER_FORM=%s: sample or pair", f);
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
-    (void)hipGetLastError();
-    return set_err(OLPE_EHIP, "no HIP device %d (%d visible)", device, ndev);
-  }
-  HIPCHK(hipSetDevice(device));
+  if ((rc = open_device(device))) return rc;
   olpe_corner *h = new olpe_corner;
-  h->device = device;
   h->ncols = ncols;
   h->nb1 = nb1;
   h->nb2 = nb2;
@@ -384,10 +346,7 @@ int olpe_corner_create(int device, int ncols, const double *edges1, int nb1,
     for (int j = i + 1; j < ncols; ++j) tab.push_back((unsigned short)((i << 8) | j));
   const std::vector<double2> g1 = guesses(edges1, ncols, nb1), g2 = guesses(edges2, ncols, nb2);
   const size_t b1 = (size_t)ncols * (nb1 + 1) * 8, b2 = (size_t)ncols * (nb2 + 1) * 8;
-  rc = OLPE_OK;
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev, hipEventDisableTiming) != hipSuccess)
-    rc = set_err(OLPE_EHIP, "stream / event creation failed");
+  rc = fold_open(h, device);
   if (!rc) rc = alloc((void **)&h->d_e1, b1, "the 1-D edges");
   if (!rc) rc = alloc((void **)&h->d_e2, b2, "the 2-D edges");
   if (!rc) rc = alloc((void **)&h->d_g1, (size_t)ncols * sizeof(double2), "the 1-D guesses");
@@ -415,14 +374,7 @@ int olpe_corner_create(int device, int ncols, const double *edges1, int nb1,
 
 void olpe_corner_destroy(olpe_corner *h) {
   if (!h) return;
-  (void)hipSetDevice(h->device);
-  if (h->ev_pending) (void)hipEventSynchronize(h->ev);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  void *bufs[] = {h->d_e1, h->d_e2, h->d_g1, h->d_g2, h->d_tab, h->d_cnt, h->d_stage};
-  for (void *b : bufs)
-    if (b) (void)hipFree(b);
-  if (h->ev) (void)hipEventDestroy(h->ev);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
+  fold_close(h, {h->d_e1, h->d_e2, h->d_g1, h->d_g2, h->d_tab, h->d_cnt, h->d_stage});
   delete h;
 }
 
@@ -431,27 +383,15 @@ int olpe_corner_fold_ctx(olpe_corner *h, olpe_ctx *c) {
   if (c->device != h->device || c->ps != h->ncols)
     return set_err(OLPE_EINVAL, "context of device %d, PS %d; corner of device %d, %d columns",
                    c->device, c->ps, h->device, h->ncols);
-  if (!c->d_state || !c->launches) return set_err(OLPE_ESTATE, "no sampler launch yet");
-  if (h->last_ctx == c && h->last_launch == c->launches)
-    return set_err(OLPE_ESTATE, "the last launch's rows are already folded");
+  int rc;
+  if ((rc = fold_check(h, c))) return rc;
   const long long n = (long long)c->W * c->chain_rows;
   HIPCHK(hipSetDevice(h->device));
-  h->last_ctx = c;
-  h->last_launch = c->launches;
+  fold_mark(h, c);
   if (n == 0) return OLPE_OK;
-  // on the sampler's stream, behind the launch and whatever this object has in flight
-  // (an earlier fold on another context's stream included: drain() then waits for one
-  // event only)
-  if (h->ev_pending) {
-    HIPCHK(hipStreamWaitEvent(h->stream, h->ev, 0));
-    h->ev_pending = false;
-  }
-  HIPCHK(hipEventRecord(h->ev, h->stream));
-  HIPCHK(hipStreamWaitEvent(c->stream, h->ev, 0));
-  int rc;
+  if ((rc = fold_enter(h, c))) return rc;
   if ((rc = launch_fold(h, c->stream, c->d_chain, n))) return rc;   // [W][nrec][PS]: n rows
-  HIPCHK(hipEventRecord(h->ev, c->stream));
-  h->ev_pending = true;
+  if ((rc = fold_leave(h, c))) return rc;
   h->n += (unsigned long long)n;
   return OLPE_OK;
 }
@@ -460,11 +400,8 @@ int olpe_corner_fold_rows(olpe_corner *h, const double *rows, long long nsamples
   if (!h || nsamples < 0 || (nsamples > 0 && !rows)) return set_err(OLPE_EINVAL, "bad argument");
   if (nsamples == 0) return OLPE_OK;
   HIPCHK(hipSetDevice(h->device));
-  if (h->ev_pending) {
-    HIPCHK(hipStreamWaitEvent(h->stream, h->ev, 0));
-    h->ev_pending = false;
-  }
   int rc;
+  if ((rc = wait_pending(h))) return rc;
   for (long long s0 = 0; s0 < nsamples; s0 += kStageSamples) {
     const long long ns = std::min(kStageSamples, nsamples - s0);
     HIPCHK(hipMemcpyAsync(h->d_stage, rows + (size_t)s0 * h->ncols, (size_t)ns * h->ncols * 8,
@@ -513,8 +450,7 @@ int olpe_corner_reset(olpe_corner *h) {
   if ((rc = drain(h))) return rc;
   HIPCHK(hipMemset(h->d_cnt, 0, h->ncount * 8));
   h->n = 0;
-  h->last_ctx = nullptr;
-  h->last_launch = 0;
+  fold_forget(h);
   return OLPE_OK;
 }
 

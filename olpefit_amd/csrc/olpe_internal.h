@@ -92,6 +92,13 @@ struct olpe_ctx {
 namespace olpe {
 int set_err(int code, const char *fmt, ...);
 }
+// a failed HIP call ends the calling function with OLPE_EHIP and the call's text
+#define HIPCHK(expr)                                                                    \
+  do {                                                                                  \
+    hipError_t e_ = (expr);                                                             \
+    if (e_ != hipSuccess)                                                               \
+      return ::olpe::set_err(OLPE_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+  } while (0)
 void olpe_comm_release(olpe_ctx *c);
 // the collectives' word buffer with its poisoned defaults (olpe_comm.hip; olpe_create)
 int olpe_comm_setup(olpe_ctx *c);

@@ -33,13 +33,6 @@ using olpe::set_err;
 
 namespace {
 
-#define HIPCHK(expr)                                                                    \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess)                                                               \
-      return set_err(OLPE_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_));         \
-  } while (0)
-
 constexpr int kThreads = 256;
 constexpr int kWalkersPerBlock = 256;    // summary stage 1: walkers per block
 

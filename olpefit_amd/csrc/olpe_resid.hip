@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "../../include/olpe.h"
+#include "olpe_fold.h"
 #include "olpe_internal.h"
 
 // The sampler's device functions, by #include only.  In a namespace of this unit's: the
@@ -48,20 +49,14 @@ namespace olpe_resid_dev {
 }
 namespace dev = olpe_resid_dev::olpe;
 
-using olpe::set_err;
+using namespace olpe;
 
-struct olpe_resid {
-  int device = 0;
+struct olpe_resid : FoldBase {
   int n = 0, nsrc = 2, bkgd_mode = 0, ps = 17;
   int rows = 16;                // tile height of the fold kernel (8 or 16)
   int piece_blocks = 0;         // blocks of kB samples per piece
   size_t npix = 0;
   bool explicit_pivot = false;  // the pivot came with olpe_resid_create
-  hipStream_t stream = nullptr;
-  hipEvent_t ev = nullptr;      // the last fold on a sampler's stream
-  bool ev_pending = false;
-  const olpe_ctx *last_ctx = nullptr;
-  long long last_launch = 0;
   double2 *d_DE = nullptr;      // [npix] the context's staged cutout
   double *d_sum = nullptr;      // [2][npix] S1, S2
   double *d_pivimg = nullptr;   // [npix] R
@@ -78,13 +73,6 @@ struct olpe_resid {
 };
 
 namespace {
-
-#define HIPCHK(expr)                                                                    \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess)                                                               \
-      return set_err(OLPE_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_));         \
-  } while (0)
 
 constexpr int kB = 256;                        // samples per block: the unit of summation order
 constexpr int kThreads = 256;
@@ -480,15 +468,6 @@ __global__ __launch_bounds__(kThreads) void resid_finalize_kernel(
   if (t == 0) fin[blockIdx.x] = FinPart{s_4[0], s_6[0], s_m[0], s_c[0], s_i[0]};
 }
 
-int alloc(void **p, size_t bytes, const char *what) {
-  if (hipMalloc(p, bytes) != hipSuccess) {
-    *p = nullptr;
-    (void)hipGetLastError();
-    return set_err(OLPE_ENOMEM, "hipMalloc(%zu bytes) for %s", bytes, what);
-  }
-  return OLPE_OK;
-}
-
 int tiles_of(const olpe_resid *r) { return ((r->n + 63) / 64) * ((r->n + r->rows - 1) / r->rows); }
 
 template <int NSRC>
@@ -553,16 +532,6 @@ bool finite_params(const double *v, int np) {
   return true;
 }
 
-// everything this object has in flight is done when this returns
-int drain(olpe_resid *r) {
-  if (r->ev_pending) {
-    HIPCHK(hipEventSynchronize(r->ev));
-    r->ev_pending = false;
-  }
-  HIPCHK(hipStreamSynchronize(r->stream));
-  return OLPE_OK;
-}
-
 int read_words(olpe_resid *r, unsigned long long *w) {
   HIPCHK(hipMemcpy(w, r->d_words, kWords * 8, hipMemcpyDeviceToHost));
   return OLPE_OK;
@@ -595,7 +564,6 @@ int olpe_resid_create(olpe_ctx *c, const double *pivot, olpe_resid **out) {
                    "takes 65535", c->n, c->n, tiles, rows);
   HIPCHK(hipSetDevice(c->device));
   olpe_resid *r = new olpe_resid;
-  r->device = c->device;
   r->n = c->n;
   r->nsrc = c->nsrc;
   r->bkgd_mode = c->bkgd_mode;
@@ -605,10 +573,7 @@ int olpe_resid_create(olpe_ctx *c, const double *pivot, olpe_resid **out) {
   r->piece_blocks = (int)std::min<size_t>(kMaxPieceBlocks, std::max<size_t>(1, kPartBudget / per_block));
   const size_t ks = 12 * (size_t)c->nsrc + 1, pb = (size_t)r->piece_blocks;
   const size_t finblocks = (npix + kThreads - 1) / kThreads;
-  int rc = OLPE_OK;
-  if (hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&r->ev, hipEventDisableTiming) != hipSuccess)
-    rc = set_err(OLPE_EHIP, "stream / event creation failed");
+  int rc = fold_open(r, c->device);
   if (!rc) rc = alloc((void **)&r->d_DE, npix * sizeof(double2), "the cutout");
   if (!rc) rc = alloc((void **)&r->d_sum, 2 * npix * 8, "the shifted sums");
   if (!rc) rc = alloc((void **)&r->d_pivimg, npix * 8, "the pivot image");
@@ -646,15 +611,8 @@ int olpe_resid_create(olpe_ctx *c, const double *pivot, olpe_resid **out) {
 
 void olpe_resid_destroy(olpe_resid *r) {
   if (!r) return;
-  (void)hipSetDevice(r->device);
-  if (r->ev_pending) (void)hipEventSynchronize(r->ev);
-  if (r->stream) (void)hipStreamSynchronize(r->stream);
-  void *bufs[] = {r->d_DE, r->d_sum, r->d_pivimg, r->d_pivot, r->d_best, r->d_words, r->d_info,
-                  r->d_boff, r->d_desc, r->d_part, r->d_planes, r->d_fin, r->d_stage};
-  for (void *b : bufs)
-    if (b) (void)hipFree(b);
-  if (r->ev) (void)hipEventDestroy(r->ev);
-  if (r->stream) (void)hipStreamDestroy(r->stream);
+  fold_close(r, {r->d_DE, r->d_sum, r->d_pivimg, r->d_pivot, r->d_best, r->d_words, r->d_info,
+                 r->d_boff, r->d_desc, r->d_part, r->d_planes, r->d_fin, r->d_stage});
   delete r;
 }
 
@@ -667,31 +625,20 @@ int olpe_resid_fold_ctx(olpe_resid *r, olpe_ctx *c, int row_step, int walker_ste
     return set_err(OLPE_EINVAL, "context of device %d, side %d, %d sources, bkgd_mode %d; this "
                    "object of device %d, side %d, %d sources, bkgd_mode %d", c->device, c->n,
                    c->nsrc, c->bkgd_mode, r->device, r->n, r->nsrc, r->bkgd_mode);
-  if (!c->d_state || !c->launches) return set_err(OLPE_ESTATE, "no sampler launch yet");
-  if (r->last_ctx == c && r->last_launch == c->launches)
-    return set_err(OLPE_ESTATE, "the last launch's rows are already folded");
+  int rc;
+  if ((rc = fold_check(r, c))) return rc;
   HIPCHK(hipSetDevice(r->device));
-  r->last_ctx = c;
-  r->last_launch = c->launches;
+  fold_mark(r, c);
   // rows 0, row_step, ... of walkers 0, walker_step, ... of the chain [W][nrec][PS],
   // walker-major: indexing only
   const long long nr = (c->chain_rows + row_step - 1) / row_step;
   const long long nw = ((long long)c->W + walker_step - 1) / walker_step;
   if (nr == 0 || nw == 0) return OLPE_OK;
-  // on the sampler's stream, behind the launch and whatever this object has in flight
-  if (r->ev_pending) {
-    HIPCHK(hipStreamWaitEvent(r->stream, r->ev, 0));
-    r->ev_pending = false;
-  }
-  HIPCHK(hipEventRecord(r->ev, r->stream));
-  HIPCHK(hipStreamWaitEvent(c->stream, r->ev, 0));
+  if ((rc = fold_enter(r, c))) return rc;
   const RowMap m{c->d_chain, nr, (long long)walker_step * c->chain_rows * c->ps,
                  (long long)row_step * c->ps};
-  int rc;
   if ((rc = launch_fold(r, c->stream, m, nr * nw))) return rc;
-  HIPCHK(hipEventRecord(r->ev, c->stream));
-  r->ev_pending = true;
-  return OLPE_OK;
+  return fold_leave(r, c);
 }
 
 int olpe_resid_fold_rows(olpe_resid *r, const double *rows, long long nsamples) {
@@ -705,10 +652,7 @@ int olpe_resid_fold_rows(olpe_resid *r, const double *rows, long long nsamples) 
   if (!r->d_stage &&
       (rc = alloc((void **)&r->d_stage, (size_t)piece * r->ps * 8, "the row upload")))
     return rc;
-  if (r->ev_pending) {
-    HIPCHK(hipStreamWaitEvent(r->stream, r->ev, 0));
-    r->ev_pending = false;
-  }
+  if ((rc = wait_pending(r))) return rc;
   for (long long s0 = 0; s0 < nsamples; s0 += piece) {
     const long long ns = std::min(piece, nsamples - s0);
     HIPCHK(hipMemcpyAsync(r->d_stage, rows + (size_t)s0 * r->ps, (size_t)ns * r->ps * 8,
@@ -802,8 +746,7 @@ int olpe_resid_reset(olpe_resid *r) {
   w[kWHavePivot] = r->explicit_pivot;          // a pivot given at create stays
   HIPCHK(hipMemset(r->d_sum, 0, 2 * r->npix * 8));
   HIPCHK(hipMemcpy(r->d_words, w, kWords * 8, hipMemcpyHostToDevice));
-  r->last_ctx = nullptr;
-  r->last_launch = 0;
+  fold_forget(r);
   return OLPE_OK;
 }
 

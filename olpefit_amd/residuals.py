@@ -20,16 +20,13 @@ import ctypes as C
 import numpy as np
 
 from . import _lib, fitsio
+from ._handle import Handle, _pd, load_npz  # noqa: F401  (load_npz: Residuals.save's reader)
 from ._lib import check
 
 PLANES = ("mean_model", "std_model", "best_model", "resid", "nresid", "mean_resid",
           "mean_nresid")
 SCALARS = ("samples", "n_bad", "pixels", "best_chi2", "chi2_best_model", "chi2_mean_model",
            "max_abs_nresid", "max_abs_nresid_at")
-
-
-def _pd(a):
-    return a.ctypes.data_as(_lib._pd)
 
 
 def mean_std(pivot_image, s1, s2, n):
@@ -44,17 +41,18 @@ def mean_std(pivot_image, s1, s2, n):
     return np.asarray(pivot_image, dtype=np.float64) + m1, np.sqrt(np.maximum(var, 0.0))
 
 
-class Residuals:
+class Residuals(Handle):
     """One ``olpe_resid`` on the sampler's GPU: a copy of its staged cutout, independent of
     the sampler afterwards.  ``pivot``: the parameter vector whose model the sums are
     shifted by (the posterior mean from ``Sampler.moments_summary``, say); None takes the
     first usable row folded."""
 
+    _destroy = "olpe_resid_destroy"
+
     def __init__(self, sampler, pivot=None):
         self.n, self.nsrc, self.np_, self.ps = sampler.n, sampler.nsrc, sampler.np_, sampler.ps
         self.data = np.array(sampler._img, dtype=np.float64)
         self._lib = _lib.load()
-        self._h = None
         pv = None
         if pivot is not None:
             pv = np.ascontiguousarray(pivot, dtype=np.float64).ravel()
@@ -65,24 +63,6 @@ class Residuals:
         check(self._lib.olpe_resid_create(sampler._ctx, None if pv is None else _pd(pv),
                                           C.byref(h)))
         self._h = h
-
-    # -- lifetime -----------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.olpe_resid_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     # -- folding ------------------------------------------------------------------
     def fold(self, sampler, row_step: int = 1, walker_step: int = 1):
@@ -183,9 +163,3 @@ class Residuals:
             paths.append(f"{prefix}_{suffix}.fits")
             fitsio.write(paths[-1], img[key])
         return paths
-
-
-def load_npz(path):
-    """What ``Residuals.save`` wrote, as a dict of arrays."""
-    with np.load(path, allow_pickle=False) as z:
-        return {k: z[k] for k in z.files}

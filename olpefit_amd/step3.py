@@ -246,18 +246,12 @@ def main(argv=None, nsrc: int = 2):
         # burn-in cannot be taken out of them afterwards
         ap.error(f"--from-moments covers every recorded row (additional_burnin 1); "
                  f"-a {additional_burnin} needs the chain files")
-    if args.from_moments and args.astrometry:
-        ap.error("--astrometry needs the chain rows (a median is not a moment): "
-                 "drop --from-moments")
-    if args.from_moments and args.corner:
-        ap.error("--corner needs the chain rows (a histogram is not a moment): "
-                 "drop --from-moments")
-    if args.from_moments and args.residuals:
-        ap.error("--residuals needs the chain rows (moments are not samples): "
-                 "drop --from-moments")
-    if args.from_moments and args.autocorr:
-        ap.error("--autocorr needs the chain rows (moments hold no order): "
-                 "drop --from-moments")
+    for flag, why in (("astrometry", "a median is not a moment"),
+                      ("corner", "a histogram is not a moment"),
+                      ("residuals", "moments are not samples"),
+                      ("autocorr", "moments hold no order")):
+        if args.from_moments and getattr(args, flag):
+            ap.error(f"--{flag} needs the chain rows ({why}): drop --from-moments")
     if args.autocorr and (args.autocorr_max_lag < 64 or args.autocorr_max_lag > 1024
                           or args.autocorr_max_lag % 64):
         ap.error(f"--autocorr-max-lag {args.autocorr_max_lag}: a multiple of 64 from 64 to 1024")
@@ -321,6 +315,11 @@ def main(argv=None, nsrc: int = 2):
     return out
 
 
+def results_prefix(args, input_directory):
+    """The results directory and the frame's name: what the stages' file names begin with."""
+    return input_directory + args.image.split('/')[-1].split('.')[-3]
+
+
 def autocorr(args, chains, nsrc, input_directory, say=print):
     """The numbers behind the reference's chain plot (apf_step3.py:582-601;
     3body/apf_step3_3body.py likewise), which is read by eye: an integrated autocorrelation
@@ -331,7 +330,7 @@ def autocorr(args, chains, nsrc, input_directory, say=print):
     from . import autocorr as ac
     labels = NAMES_2 if nsrc == 2 else NAMES_3
     say('Computing autocorrelation times...')
-    path = input_directory + args.image.split('/')[-1].split('.')[-3] + '_autocorr.npz'
+    path = results_prefix(args, input_directory) + '_autocorr.npz'
     with ac.Autocorr(chains.shape[2], args.autocorr_max_lag, labels=labels) as a:
         a.fold_rows(chains, time_major=True)
         st, res = a.save(path, c=args.autocorr_c)
@@ -363,7 +362,7 @@ def corner(args, chains, nsrc, input_directory, say=print):
     from . import corner as cn
     labels = cn.LABELS_2 if nsrc == 2 else cn.LABELS_3
     say('Creating a corner plot...')                                    # :605
-    path = input_directory + args.image.split('/')[-1].split('.')[-3] + '_corner.npz'  # :643
+    path = results_prefix(args, input_directory) + '_corner.npz'        # :643
     with cn.Corner(cn.Corner.ranges_of(chains), bins=args.corner_bins,
                    fine_bins=args.corner_fine_bins, labels=labels) as c:
         c.fold_rows(chains)
@@ -393,7 +392,7 @@ def residuals(args, chains, nsrc, input_directory, say=print):
     from .core import Sampler
     image, hdr = fitsio.getdata_header(args.image)
     say('Building model and residual images...')
-    prefix = input_directory + args.image.split('/')[-1].split('.')[-3]
+    prefix = results_prefix(args, input_directory)
     with Sampler(image, hdr["ITIME"], hdr["COADDS"], hdr["MULTISAM"], hdr["SAMPMODE"],
                  nsrc=nsrc, bkgd_mode=args.bkgd_mode) as s, rs.Residuals(s) as r:
         r.fold_rows(chains[::args.residuals_thin])

@@ -1,15 +1,7 @@
 """The autocorrelation kernels (olpe_acf.hip) use no scratch and the fold kernel fits the
 occupancy its design relies on: checked from the compiler's resource usage, as
 test_corner_resources does for the corner folds."""
-import os
-import re
-import shutil
-import subprocess
-
-import pytest
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+from resource_usage import kernel_resources
 
 
 def test_acf_kernels_have_no_scratch_and_fit_their_occupancy():
@@ -20,27 +12,7 @@ def test_acf_kernels_have_no_scratch_and_fit_their_occupancy():
     allocated in steps of 8: 96.  With two passes (max_lag > 512) a staged
     column is at least 10,880 bytes, so a workgroup has at most 7 waves and two workgroups 14,
     four on the fullest SIMD: 128 VGPRs."""
-    if not (os.path.exists(HIPCC) or shutil.which("hipcc")):
-        pytest.skip("hipcc not available")
-    from olpefit_amd import build
-    src = os.path.join(build.CSRC, "olpe_acf.hip")
-    assert src in build.SOURCES
-    flags = [f for f in build.FLAGS if f not in ("-shared", "-fPIC", "-Wall",
-                                                  "-Wno-unused-function")]
-    cmd = [HIPCC, *flags, "--cuda-device-only", "-c", "-o", os.devnull, src,
-           "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600).stderr
-    res, name = {}, None
-    for line in out.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|VGPRs Spill|"
-                      r"Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and name:
-            res[name][m.group(1)] = int(m.group(2))
+    res = kernel_resources("olpe_acf.hip")
     for kern, count in (("acf_stats_kernel", 1), ("acf_fold_kernel", 2),
                         ("acf_reduce_kernel", 1), ("acf_reduce0_kernel", 1)):
         hits = [v for k, v in res.items() if kern + "E" in k or kern + "I" in k]
