@@ -2,14 +2,16 @@
 20-column chains and Gelman-Rubin statistics; with --astrometry also the separation /
 position angle / RA / Dec of b and c about a, on the GPU, with --corner the corner
 plot's histograms and quantile brackets, with --residuals the posterior's model and
-residual images, and with --autocorr the chains' autocorrelation times and effective sample
-sizes; see olpefit_amd/step3.py).
+residual images, with --autocorr the chains' autocorrelation times and effective sample
+sizes, and with --photometry the companions' flux ratios and delta magnitudes, the FWHM and
+the sources' S/N; see olpefit_amd/step3.py).
 
     python 3body/apf_step3_3body.py <image> <system> -s <walkers> [-a <burn>]
         [--astrometry [--distortion X.fits Y.fits] [--delta-r MAS] [--prepost pre|post]]
         [--corner [--corner-bins N] [--corner-fine-bins N]]
         [--residuals [--residuals-thin N] [--bkgd-mode 0|1]]
         [--autocorr [--autocorr-max-lag N] [--autocorr-c X]]
+        [--photometry [--photometry-thin N]]
 """
 import os
 import sys

@@ -6,14 +6,18 @@ the corner plot's 1-D / 2-D histograms and quantile brackets, counted on the GPU
 to <frame>_corner.npz; with --residuals the posterior mean / scatter of the model and the
 best sample's residual images, folded on the GPU and written to <frame>_residuals.npz and
 four FITS files; with --autocorr an integrated autocorrelation time and effective sample size
-per parameter, the lag sums folded on the GPU and written to <frame>_autocorr.npz (nothing is
-drawn).
+per parameter, the lag sums folded on the GPU and written to <frame>_autocorr.npz; with
+--photometry the companion's flux ratio and delta magnitude, the primary's flux, the FWHM and
+the core fraction of every chain row, reduced on the GPU, and the reference's aperture S/N and
+FWHM numbers, written to <frame>_photometry.npz and, with --astrometry, into the S/N and FWHM
+fields of the epoch_grand_pasep line (nothing is drawn).
 
     python apf_step3.py <dir>/N2.<date>.<frame>.LDIF.fits <system> -s <walkers> [-a <burn>]
         [--astrometry [--distortion X.fits Y.fits] [--delta-r MAS] [--prepost pre|post]]
         [--corner [--corner-bins N] [--corner-fine-bins N]]
         [--residuals [--residuals-thin N] [--bkgd-mode 0|1]]
         [--autocorr [--autocorr-max-lag N] [--autocorr-c X]]
+        [--photometry [--photometry-thin N]]
 """
 import os
 import sys

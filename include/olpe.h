@@ -301,7 +301,8 @@ int olpe_moments_summary(olpe_ctx *ctx, const double *centre, double *out);
  * files nor a host pass over them.  An olpe_astrom belongs to a device, not to a sampler
  * context: step 3 uses it on chains read from files as well.  Calls on one object are not
  * thread-safe.  Not covered: computing deltaR (the name resolver, the AltAz transform and
- * atm_corr, :348-391), medians over several objects, and the photometry (:452-511). */
+ * atm_corr, :348-391) and medians over several objects.  The photometry (:452-511) is
+ * olpe_phot's, below. */
 typedef struct olpe_astrom olpe_astrom;
 /* Doubles per pair of olpe_astrom_finalize's output:
  *   [0] np.median(sep_corrected), [1] np.std(sep_corrected)              (:436)
@@ -517,6 +518,81 @@ int olpe_acf_add(olpe_acf *h, int ncols, int max_lag, unsigned long long n,
                  unsigned long long series, unsigned long long skipped, const double *C_in);
 /* Zeroes the state (apf_step3.py:582-601 starts over). */
 int olpe_acf_reset(olpe_acf *h);
+
+/* --- photometry posteriors (apf_step3.py:452-511; the model of apf_step2.py:78-124) ----
+ * How bright the companion is relative to the star, with its uncertainty, and the PSF's
+ * width: what the reference's photometry block (apf_step3.py:452-511; 3body
+ * /apf_step3_3body.py:520-569) takes from the image and from 100 rows, taken from every
+ * chain row instead.  In build_analytical_model (apf_step2.py:78-124; 3body :78-125) every
+ * source shares ampratio q, the widths sx, sy, sx2, sy2, the angles and the amplitude
+ * offset b (p[9]; 3body p[12]), so source k integrates to F_k = 2 pi (A_k - b) [(1 - q) sx
+ * sy + q sx2 sy2] and the flux ratio of companion k to the primary is (A_k - b) / (A_0 - b).
+ * An olpe_phot turns chain rows into Q = 2 (nsrc - 1) + 5 planes of samples on the device,
+ * stored [rows][walkers] as the astrometry samples are, in this order:
+ *   per companion k = 1 .. nsrc - 1:  flux_ratio_k = (A_k - b) / (A_0 - b),
+ *                                     dmag_k = -2.5 log10(flux_ratio_k)
+ *   flux_primary      F_0, counts px^2
+ *   fwhm_major        2.355 max(sx, sy) pixscale, mas (what apf_step3.py:463-469 means to
+ *                     take; what it takes is photometry.reference_fwhm's, on the host)
+ *   fwhm_minor        2.355 min(sx, sy) pixscale
+ *   fwhm_wide_major   2.355 max(sx2, sy2) pixscale
+ *   core_fraction     (1 - q) sx sy / [(1 - q) sx sy + q sx2 sy2]
+ * The operation order is stated in olpe_phot.hip; all but log10 is exact IEEE arithmetic.
+ * A row is unusable if a column it reads is non-finite, if A_0 - b <= 0 or if a width is
+ * <= 0: it stores NaN in every plane and is counted once.  A companion with A_k - b <= 0
+ * keeps its ratio and has a NaN dmag_k.  NaN takes part in no statistic, so every plane has
+ * its own count.  An olpe_phot belongs to a device, not to a sampler context.  Calls on one
+ * object are not thread-safe.  Not covered: the aperture S/N of apf_step3.py:476-511 (per
+ * image, not per sample: photometry.aperture_snr on the host), magnitudes on a
+ * photometric system, a checkpoint of the store, a collective over it. */
+typedef struct olpe_phot olpe_phot;
+/* Doubles per plane of olpe_phot_finalize's output for nprobs probabilities:
+ *   [0] n, the samples that are not NaN  [1] np.mean  [2] np.std (ddof 0; exactly 0 where
+ *   all n are one value)  [3] min  [4] max  [5] the reads of the plane the select made
+ *   [6 + 2 j], [7 + 2 j] the order statistics floor((n - 1) p_j) and ceil((n - 1) p_j) of
+ *   the n samples (what np.percentile interpolates between, apf_step3.py:435-437's
+ *   np.median being p = 0.5).  With n = 0 everything but [0] and [5] is NaN. */
+#define OLPE_PHOT_LEN(nprobs) (6 + 2 * (nprobs))
+/* The set-up for one frame of apf_step3.py:452-470's numbers: variant 2 (apf_step2.py:
+ * 78-97's columns: A at 6, 7, q 8, b 9, widths 10-13) or 3 (3body :78-98: A at 8-10, q 11,
+ * b 12, widths 13-16); ps doubles per chain row; pixscale mas per pixel (:224 / :231); the
+ * store holds row_cap rows of walkers walkers (8 Q bytes each).  Invalid arguments are
+ * OLPE_EINVAL before any GPU call; a capacity the device cannot hold is OLPE_ENOMEM naming
+ * its bytes. */
+int olpe_phot_create(int device, int variant, int ps, double pixscale, long long walkers,
+                     long long row_cap, olpe_phot **out);
+/* Frees the samples of apf_step3.py:452-470's columns (waits for its folds in flight). */
+void olpe_phot_destroy(olpe_phot *p);
+/* The planes (apf_step2.py:78-124's model, apf_step3.py:463-469's FWHM) for rows 0,
+ * row_step, 2 row_step, ... of ctx's last launch, read from its device chain in place
+ * (async on the context's stream, no host copy).  Once per launch: OLPE_ESTATE if this
+ * launch was folded already, and if the store would overflow (nothing is folded then and
+ * the launch stays unfolded); OLPE_EINVAL for a context of another device, walker count,
+ * PS or source count. */
+int olpe_phot_fold_ctx(olpe_phot *p, olpe_ctx *ctx, int row_step);
+/* The same (apf_step2.py:78-124, apf_step3.py:463-469) for host rows [nrows][walkers][ps]
+ * as step 3 collates them (apf_step3.py:169-205, step3.load_chains), uploaded whole in
+ * pieces of at most 64 MiB.  OLPE_ESTATE if the store would overflow. */
+int olpe_phot_fold_rows(olpe_phot *p, const double *rows, long long nrows);
+/* Rows folded per walker so far (len(sigmax) of apf_step3.py:458). */
+int olpe_phot_rows(olpe_phot *p, long long *rows);
+/* Unusable rows so far (the NaN seed row of apf_step2.py:278-279 is one per walker).
+ * Waits for the folds in flight. */
+int olpe_phot_unusable(olpe_phot *p, long long *n);
+/* The summary of every plane (np.mean / np.std as apf_step3.py:470 takes them, the order
+ * statistics np.median of :435-437 is made of) for probs[0 .. nprobs) in [0, 1], nprobs <=
+ * 16: out [Q][OLPE_PHOT_LEN(nprobs)].  Every sum runs over the store in a fixed order, so
+ * the result does not depend on how the rows were split over folds; the select is exact.
+ * The store is left as it is: more folds and another finalize may follow.  OLPE_ESTATE
+ * with no row folded. */
+int olpe_phot_finalize(olpe_phot *p, const double *probs, int nprobs, double *out);
+/* One plane's samples (apf_step3.py:469's FWHM array and its like) into out[0 .. n), n =
+ * rows x walkers, sample (row r, walker w) at r * walkers + w.  Waits for the folds in
+ * flight. */
+int olpe_phot_samples(olpe_phot *p, int plane, double *out);
+/* Empties the store and the unusable count (apf_step3.py:452-470 starts over); the launch
+ * folded last may be folded again. */
+int olpe_phot_reset(olpe_phot *p);
 
 #ifdef __cplusplus
 }

@@ -116,6 +116,15 @@ SIGNATURES = {
     "olpe_acf_get": (_i, [_P, _pu64, _pu64, _pu64, _pd]),
     "olpe_acf_add": (_i, [_P, _i, _i, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, _pd]),
     "olpe_acf_reset": (_i, [_P]),
+    "olpe_phot_create": (_i, [_i, _i, _i, _d, _ll, _ll, C.POINTER(_P)]),
+    "olpe_phot_destroy": (None, [_P]),
+    "olpe_phot_fold_ctx": (_i, [_P, _P, _i]),
+    "olpe_phot_fold_rows": (_i, [_P, _pd, _ll]),
+    "olpe_phot_rows": (_i, [_P, _pll]),
+    "olpe_phot_unusable": (_i, [_P, _pll]),
+    "olpe_phot_finalize": (_i, [_P, _pd, _i, _pd]),
+    "olpe_phot_samples": (_i, [_P, _i, _pd]),
+    "olpe_phot_reset": (_i, [_P]),
     "olpe_moments_fault": (_i, [_P, _i]),
     "olpe_test_hold_handoff": (_i, [_P, _i]),
 }

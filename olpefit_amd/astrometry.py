@@ -8,8 +8,9 @@ by delta RA / Dec.  ``Astrometry`` keeps the samples on the GPU and reduces them
 the host does the reference's scalar work only (``from_header``).
 
 Not covered: computing ``deltaR`` itself (the name resolver, the AltAz transform and
-``atm_corr``, apf_step3.py:348-391: pass it as ``delta_r``), medians over several objects,
-the photometry fields of the output lines (written as ``nan``) and the plots.
+``atm_corr``, apf_step3.py:348-391: pass it as ``delta_r``), medians over several objects
+and the plots.  The photometry fields of the output lines are ``photometry.py``'s
+(``pasep_line(photometry=...)``; ``nan`` without).
 """
 from __future__ import annotations
 
@@ -89,16 +90,26 @@ def py2_str(x) -> str:
     return s
 
 
-def pasep_line(koaid, results, rc_mean, rc_std, variant: int = 2) -> str:
+def pasep_line(koaid, results, rc_mean, rc_std, variant: int = 2, photometry=None) -> str:
     """The ``epoch_grand_pasep`` line (apf_step3.py:517-527; 3body :575-590) without its
-    newline.  The S/N and FWHM fields (photometry: not covered) are ``nan``."""
+    newline.  ``photometry`` carries the S/N and FWHM fields (:522-525; 3body :584-588) as
+    ``photometry.reference_numbers`` returns them: ``snr`` (the primary's first, one per
+    source), ``fwhm_mean``, ``fwhm_std``; without it they are ``nan``."""
     nan = float("nan")
+    nsnr = 2 if variant == 2 else 3
     f = [str(koaid)]
     for r in results:
         f += [py2_str(r["sep_median"]), py2_str(r["sep_std"]), py2_str(r["pa_median"]),
               py2_str(r["pa_std"])]
-    f += [py2_str(nan)] * (2 if variant == 2 else 3)       # star / companion S/N
-    f += [py2_str(nan), py2_str(nan)]                       # FWHM mean, std
+    if photometry is None:
+        snr, fwhm = [nan] * nsnr, [nan, nan]
+    else:
+        snr = list(photometry["snr"])
+        fwhm = [photometry["fwhm_mean"], photometry["fwhm_std"]]
+        if len(snr) != nsnr:
+            raise ValueError(f"{len(snr)} S/N values for {nsnr} sources")
+    f += [py2_str(v) for v in snr]                          # star / companion S/N
+    f += [py2_str(v) for v in fwhm]                         # FWHM mean, std
     f += [py2_str(rc_mean), py2_str(rc_std)]
     return " , ".join(f)
 

@@ -15,7 +15,7 @@
 //     mean(pa), then -- the host having taken the reference's scalar decisions -- the
 //     per-sample refraction correction in place, the means and the squared deviations
 //     (two passes, as np.std), and the exact medians by radix select on order-preserving
-//     64-bit keys (histograms per workgroup in LDS, merged with integer atomics).
+//     64-bit keys (olpe_select.h, shared with olpe_phot.hip).
 // Device libm's atan2 / tan / atan / sin / cos differ from the host's by a few ulp: the
 // per-sample values are compared to a tolerance, the select exactly.
 #include <hip/hip_runtime.h>
@@ -29,6 +29,7 @@
 #include "../../include/olpe.h"
 #include "olpe_fold.h"
 #include "olpe_internal.h"
+#include "olpe_select.h"
 
 using namespace olpe;
 
@@ -50,7 +51,7 @@ struct olpe_astrom : FoldBase {
   double *d_part = nullptr;   // [4][nblk] reduction partials
   double *d_out = nullptr;    // [8] reduction results
   unsigned long long *d_words = nullptr;  // [0] bad rows, [1..4] min / max keys of sep and pa, [5] next key
-  unsigned long long *d_hist = nullptr;   // [kBins]
+  unsigned long long *d_hist = nullptr;   // [kSelBins]
   double *d_stage = nullptr;  // upload staging of fold_rows
   size_t stage_cap = 0;
 };
@@ -60,9 +61,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kPer = 16;                       // samples per thread of a reduction block
 constexpr long long kChunk = kThreads * kPer;  // samples per reduction block
-constexpr int kDigit = 11;                     // radix-select digit: 2048 bins, 8 KiB of LDS
-constexpr int kBins = 1 << kDigit;
-constexpr int kSelBlocks = 1024;
 constexpr double kDeg2Rad = M_PI / 180.0;      // np.radians / np.degrees multiply by these
 constexpr double kRad2Deg = 180.0 / M_PI;
 
@@ -156,20 +154,6 @@ __global__ __launch_bounds__(kThreads) void astrom_fold_kernel(
     }
   }
   if (nbad) atomicAdd(bad, (unsigned long long)nbad);
-}
-
-// order-preserving key of a double (negative values below positive ones, -0.0 just
-// below +0.0) and its inverse
-__host__ __device__ __forceinline__ unsigned long long okey(double x) {
-  unsigned long long b;
-  memcpy(&b, &x, 8);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-double okey_inv(unsigned long long k) {
-  const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-  double x;
-  memcpy(&x, &b, 8);
-  return x;
 }
 
 struct CorrCfg {
@@ -303,51 +287,6 @@ __global__ __launch_bounds__(kThreads) void astrom_reduce_stage2(const double *_
   if (threadIdx.x == 0) out[blockIdx.x] = a;
 }
 
-// one digit of the radix select: the histogram of digit (d >> shift) & (bins - 1) of the
-// keys d = okey(x) - kmin whose bits above `pshift` equal `prefix` (all keys when !filt)
-__global__ __launch_bounds__(kThreads) void astrom_hist_kernel(
-    const double *__restrict__ x, long long n, unsigned long long kmin, int shift, int bins,
-    int filt, int pshift, unsigned long long prefix, unsigned long long *__restrict__ ghist) {
-  __shared__ unsigned h[kBins];
-  for (int i = threadIdx.x; i < kBins; i += kThreads) h[i] = 0;
-  __syncthreads();
-  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n;
-       i += (long long)gridDim.x * kThreads) {
-    const unsigned long long d = okey(x[i]) - kmin;
-    if (!filt || (d >> pshift) == prefix) atomicAdd(&h[(unsigned)(d >> shift) & (bins - 1)], 1u);
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < bins; i += kThreads)
-    if (h[i]) atomicAdd(&ghist[i], (unsigned long long)h[i]);
-}
-
-// the smallest key above `key`
-__global__ __launch_bounds__(kThreads) void astrom_next_kernel(const double *__restrict__ x,
-                                                               long long n,
-                                                               unsigned long long key,
-                                                               unsigned long long *__restrict__ out) {
-  __shared__ unsigned long long lo[kThreads];
-  unsigned long long m = ~0ull;
-  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n;
-       i += (long long)gridDim.x * kThreads) {
-    const unsigned long long k = okey(x[i]);
-    if (k > key && k < m) m = k;
-  }
-  lo[threadIdx.x] = m;
-  __syncthreads();
-  for (int o = kThreads / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o && lo[threadIdx.x + o] < lo[threadIdx.x])
-      lo[threadIdx.x] = lo[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) atomicMin(out, lo[0]);
-}
-
-unsigned grid_for(long long n) {
-  const long long b = (n + kThreads - 1) / kThreads;
-  return (unsigned)std::max(1ll, std::min<long long>(b, kSelBlocks));
-}
-
 // sums of `nv` values over n samples into host out[nv]
 int reduce(olpe_astrom *a, const double *x, const double *y, long long n, const RedCfg &c,
            int nv, double *out) {
@@ -363,54 +302,24 @@ int reduce(olpe_astrom *a, const double *x, const double *y, long long n, const 
   return OLPE_OK;
 }
 
-// np.median of x[0..n): the order statistics (n - 1) / 2 and n / 2 by radix select below
-// the common prefix of the keys (kmin / kmax: their extremes), and their mean
+// np.median of x[0..n): the order statistic (n - 1) / 2 by radix select below the common
+// prefix of the keys (kmin / kmax: their extremes), the one after it where n is even, and
+// their mean (olpe_select.h)
 int median(olpe_astrom *a, const double *x, long long n, unsigned long long kmin,
            unsigned long long kmax, double *out) {
   const long long k1 = (n - 1) / 2, k2 = n / 2;
-  const unsigned long long span = kmax - kmin;
-  int pos = 0;
-  while (pos < 64 && (span >> pos) != 0) ++pos;            // bits in which the keys differ
-  unsigned long long prefix = 0, in_bin = (unsigned long long)n;
-  long long k = k1;
-  std::vector<unsigned long long> h(kBins);
-  bool first = true;
-  while (pos > 0) {
-    const int bits = pos % kDigit ? pos % kDigit : kDigit;
-    const int shift = pos - bits;
-    HIPCHK(hipMemsetAsync(a->d_hist, 0, kBins * 8, a->stream));
-    hipLaunchKernelGGL(astrom_hist_kernel, dim3(grid_for(n)), dim3(kThreads), 0, a->stream, x, n,
-                       kmin, shift, 1 << bits, first ? 0 : 1, first ? 0 : pos, prefix, a->d_hist);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h.data(), a->d_hist, (size_t)(1 << bits) * 8, hipMemcpyDeviceToHost,
-                          a->stream));
-    HIPCHK(hipStreamSynchronize(a->stream));
-    int bin = 0;
-    unsigned long long cum = 0;
-    for (; bin < (1 << bits); ++bin) {
-      if ((unsigned long long)k < cum + h[bin]) break;
-      cum += h[bin];
-    }
-    if (bin == (1 << bits)) return set_err(OLPE_EHIP, "radix select: histogram short of its rank");
-    k -= (long long)cum;
-    in_bin = h[bin];
-    prefix = (prefix << bits) | (unsigned long long)bin;
-    pos = shift;
-    first = false;
-  }
-  const unsigned long long key1 = kmin + prefix;
-  unsigned long long key2 = key1;
-  // keys <= key1: those below it (k1 - k) and its in_bin copies
-  if ((unsigned long long)k2 >= (unsigned long long)(k1 - k) + in_bin) {
-    const unsigned long long all = ~0ull;
-    HIPCHK(hipMemcpyAsync(a->d_words + 5, &all, 8, hipMemcpyHostToDevice, a->stream));
-    hipLaunchKernelGGL(astrom_next_kernel, dim3(grid_for(n)), dim3(kThreads), 0, a->stream, x, n,
-                       key1, a->d_words + 5);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&key2, a->d_words + 5, 8, hipMemcpyDeviceToHost, a->stream));
-    HIPCHK(hipStreamSynchronize(a->stream));
-  }
-  const double v1 = okey_inv(key1), v2 = okey_inv(key2);
+  SelRank r;
+  r.k = k1;
+  int rc;
+  if ((rc = select_ranks(a->stream, a->d_hist, x, n, (unsigned long long)n, kmin, kmax, &r, 1,
+                         nullptr)))
+    return rc;
+  unsigned long long key2 = r.key;
+  // keys <= r.key: those below it and its copies
+  if ((unsigned long long)k2 >= r.below + r.equal &&
+      (rc = select_next(a->stream, a->d_words + 5, x, n, r.key, kmax, &key2, nullptr)))
+    return rc;
+  const double v1 = okey_inv(r.key), v2 = okey_inv(key2);
   *out = k1 == k2 ? v1 : (v1 + v2) / 2.0;                  // np.mean of the middle pair
   return OLPE_OK;
 }
@@ -502,7 +411,7 @@ int olpe_astrom_create(int device, int variant, int ps, const int *pair_cols, in
                       "the reduction partials");
   if (!rc) rc = alloc((void **)&a->d_out, 8 * 8, "the reduction results");
   if (!rc) rc = alloc((void **)&a->d_words, 8 * 8, "the astrometry words");
-  if (!rc) rc = alloc((void **)&a->d_hist, kBins * 8, "the select histogram");
+  if (!rc) rc = alloc((void **)&a->d_hist, kSelBins * 8, "the select histogram");
   if (!rc && a->have_tab) {
     const size_t tb = (size_t)tab_ny * tab_nx * 8;
     rc = alloc((void **)&a->d_xd, tb, "the X distortion table");

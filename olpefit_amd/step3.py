@@ -183,7 +183,8 @@ def main(argv=None, nsrc: int = 2):
     below); without it nothing past the statistics runs and the outputs are unchanged.
     ``--corner`` and ``--residuals`` add the corner plot's counts and the posterior's model
     / residual images (``corner``, ``residuals`` below) in the same way, ``--autocorr`` the
-    chains' integrated autocorrelation times and effective sample sizes (``autocorr``)."""
+    chains' integrated autocorrelation times and effective sample sizes (``autocorr``),
+    ``--photometry`` the flux ratio, delta magnitude, FWHM and S/N (``photometry``)."""
     import argparse
     import json
     import sys
@@ -235,6 +236,13 @@ def main(argv=None, nsrc: int = 2):
                     help="largest lag in recorded rows (a multiple of 64, 64 to 1024)")
     ap.add_argument("--autocorr-c", type=float, default=5.0, metavar="X",
                     help="the window is the smallest M with M >= X tau(M) (emcee's c = 5)")
+    ap.add_argument("--photometry", action="store_true",
+                    help="flux ratio, delta magnitude, primary flux, FWHM and core fraction of "
+                         "every chain row (GPU), the reference's aperture S/N and FWHM (host); "
+                         "writes <frame>_photometry.npz and, with --astrometry, the S/N and "
+                         "FWHM fields of the epoch_grand_pasep line")
+    ap.add_argument("--photometry-thin", type=int, default=1, metavar="N",
+                    help="fold every N-th row after the burn-in")
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
     say = (lambda *a: None) if args.quiet else print
     ncor = int(np.int_(args.size))                                  # :76-77
@@ -249,7 +257,8 @@ def main(argv=None, nsrc: int = 2):
     for flag, why in (("astrometry", "a median is not a moment"),
                       ("corner", "a histogram is not a moment"),
                       ("residuals", "moments are not samples"),
-                      ("autocorr", "moments hold no order")):
+                      ("autocorr", "moments hold no order"),
+                      ("photometry", "a percentile is not a moment")):
         if args.from_moments and getattr(args, flag):
             ap.error(f"--{flag} needs the chain rows ({why}): drop --from-moments")
     if args.autocorr and (args.autocorr_max_lag < 64 or args.autocorr_max_lag > 1024
@@ -257,6 +266,8 @@ def main(argv=None, nsrc: int = 2):
         ap.error(f"--autocorr-max-lag {args.autocorr_max_lag}: a multiple of 64 from 64 to 1024")
     if args.residuals_thin < 1:
         ap.error(f"--residuals-thin {args.residuals_thin}: must be >= 1")
+    if args.photometry_thin < 1:
+        ap.error(f"--photometry-thin {args.photometry_thin}: must be >= 1")
     if args.from_moments:
         with open(input_directory + "posterior_summary.json") as f:
             summ = json.load(f)
@@ -301,15 +312,19 @@ def main(argv=None, nsrc: int = 2):
            "source": "moments" if args.from_moments else ("npy" if args.npy else "csv"),
            "gr_rc_mean": float(np.mean(rc)), "gr_rc_std": float(np.std(rc)),
            "parameters": stats}
+    phot, phot_ref = (photometry(args, chains, nsrc, input_directory, say) if args.photometry
+                      else (None, None))
     if args.astrometry:
         out["astrometry"] = astrometry(args, chains, nsrc, float(np.mean(rc)),
-                                       float(np.std(rc)), say)
+                                       float(np.std(rc)), say, photometry=phot_ref)
     if args.corner:
         out["corner"] = corner(args, chains, nsrc, input_directory, say)
     if args.residuals:
         out["residuals"] = residuals(args, chains, nsrc, input_directory, say)
     if args.autocorr:
         out["autocorr"] = autocorr(args, chains, nsrc, input_directory, say)
+    if phot:
+        out["photometry"] = phot
     with open(input_directory + "step3_summary.json", "w") as f:
         json.dump(out, f, indent=1)
     return out
@@ -404,25 +419,89 @@ def residuals(args, chains, nsrc, input_directory, say=print):
             "bkgd_mode": args.bkgd_mode, **scal}
 
 
-def astrometry(args, chains, nsrc, rc_mean, rc_std, say=print):
+def resolve_prepost(args):
+    """--prepost, or apf_step3.py:149-153's choice by the year the image's directory name
+    starts with."""
+    from . import astrometry as am
+    if args.prepost is not None:
+        return args.prepost
+    try:
+        return am.prepost_of(am.epoch_of(args.image))                   # :149-153
+    except (ValueError, IndexError):
+        raise ValueError(f"{args.image}: the directory name does not start with the "
+                         f"epoch's year (apf_step3.py:149); give --prepost") from None
+
+
+def photometry(args, chains, nsrc, input_directory, say=print):
+    """The photometry of the chains [N, M, PS] already read.  On the GPU
+    (photometry.Photometry): every ``--photometry-thin``-th row's flux ratio and delta
+    magnitude per companion, the primary's integrated flux, the FWHM of the narrow and the
+    wide Gaussian and the core fraction (the model of apf_step2.py:78-124; 3body :78-125),
+    summarised by median, 16 / 84 % percentiles, mean and np.std.  On the host: what the
+    reference's own block computes (apf_step3.py:452-511; 3body :520-569), FWHMmean /
+    FWHMstd over the last 100 rows and the sources' aperture S/N, which fill the pasep
+    line's fields under ``--astrometry``.  pixscale is the header's (apf_step3.py:224 /
+    :231, by ``--prepost`` or the epoch).  Writes ``<frame>_photometry.npz`` beside the
+    chain files and returns what ``step3_summary.json`` records, then the host numbers as
+    ``photometry.reference_numbers`` gives them (for ``astrometry``'s pasep line)."""
+    from . import astrometry as am, fitsio, photometry as ph
+    image, hdr = fitsio.getdata_header(args.image)
+    prepost = resolve_prepost(args)
+    pixscale = am.header_scalars(hdr, prepost)["pixscale"]
+    say('Computing photometry...')
+    thinned = chains[::args.photometry_thin]
+    with ph.Photometry(chains.shape[1], thinned.shape[0], variant=nsrc, ps=chains.shape[2],
+                       pixscale=pixscale) as p:
+        p.fold_rows(thinned)
+        res = p.finalize(ph.DEFAULT_PROBS)
+        unusable, planes = p.unusable, p.planes
+    ref = ph.reference_numbers(image, chains, pixscale, nsrc)
+    table = np.array([[res[k]["percentiles"][1], res[k]["percentiles"][0],
+                       res[k]["percentiles"][2], res[k]["mean"], res[k]["std"], res[k]["min"],
+                       res[k]["max"]] for k in planes])
+    for k, t in zip(planes, table):
+        say(f"{k:>16} median {t[0]:.10g} -{t[0] - t[1]:.6g} +{t[2] - t[0]:.6g} "
+            f"mean {t[3]:.10g} std {t[4]:.6g}")
+    say("Unusable rows:", unusable)
+    say("FWHM (reference, last 100 rows):", ref["fwhm_mean"], ref["fwhm_std"])
+    say("S/N (reference apertures):", *ref["snr"])
+    path = results_prefix(args, input_directory) + '_photometry.npz'
+    np.savez(path, planes=np.array(planes), table=table,
+             columns=np.array(["median", "p16", "p84", "mean", "std", "min", "max"]),
+             probs=np.array(ph.DEFAULT_PROBS), counts=np.array([res[k]["n"] for k in planes]),
+             unusable=np.int64(unusable), thin=np.int64(args.photometry_thin),
+             pixscale=np.float64(pixscale), snr=np.array(ref["snr"]),
+             fwhm_mean=np.float64(ref["fwhm_mean"]), fwhm_std=np.float64(ref["fwhm_std"]),
+             positions=np.array(ref["positions"]))
+
+    def num(v):                                   # JSON has no NaN
+        return float(v) if np.isfinite(v) else None
+    return {"file": path, "thin": args.photometry_thin, "prepost": prepost,
+            "pixscale": pixscale, "rows": int(thinned.shape[0]), "unusable": unusable,
+            "probs": list(ph.DEFAULT_PROBS),
+            "planes": {k: {"n": res[k]["n"], "median": num(res[k]["percentiles"][1]),
+                           "p16": num(res[k]["percentiles"][0]),
+                           "p84": num(res[k]["percentiles"][2]), "mean": num(res[k]["mean"]),
+                           "std": num(res[k]["std"]), "min": num(res[k]["min"]),
+                           "max": num(res[k]["max"])} for k in planes},
+            "reference": {"positions": ref["positions"], "snr": [num(v) for v in ref["snr"]],
+                          "fwhm_mean": num(ref["fwhm_mean"]),
+                          "fwhm_std": num(ref["fwhm_std"])}}, ref
+
+
+def astrometry(args, chains, nsrc, rc_mean, rc_std, say=print, photometry=None):
     """apf_step3.py:211-256, :283-343, :401-450 and the two result lines of :517-546
     (3body/apf_step3_3body.py:247-288, :315-390, :450-518, :575-613) for the chains
     [N, M, PS] already read: the per-sample work and every reduction on the GPU
     (astrometry.Astrometry), the header's scalars on the host.  Appends to
     ``epoch_grand_pasep`` / ``epoch_grand_radec`` beside the image and returns what
     ``step3_summary.json`` records.  deltaR is ``--delta-r`` (computing it needs a network
-    name resolver: not covered); the S/N and FWHM fields are ``nan`` (photometry: not
-    covered)."""
+    name resolver: not covered); the S/N and FWHM fields are ``photometry``'s (what
+    ``photometry()`` below returns under ``"reference"``), ``nan`` without it."""
     from . import astrometry as am, fitsio, pipeline
     image, hdr = fitsio.getdata_header(args.image)
     directory, _, _ = pipeline.image_paths(args.image)
-    prepost = args.prepost
-    if prepost is None:
-        try:
-            prepost = am.prepost_of(am.epoch_of(args.image))            # :149-153
-        except (ValueError, IndexError):
-            raise ValueError(f"{args.image}: the directory name does not start with the "
-                             f"epoch's year (apf_step3.py:149); give --prepost") from None
+    prepost = resolve_prepost(args)
     x_dist = y_dist = None
     if args.distortion:
         x_dist = np.asarray(fitsio.getdata_header(args.distortion[0])[0], dtype=np.float64)
@@ -441,7 +520,7 @@ def astrometry(args, chains, nsrc, rc_mean, rc_std, say=print):
     for r in res:
         say("r%s = " % r["pair"], r["sep_median"], "pa%s = " % r["pair"], r["pa_median"])
     koaid = hdr.get('KOAID', '')
-    pasep = am.pasep_line(koaid, res, rc_mean, rc_std, nsrc)
+    pasep = am.pasep_line(koaid, res, rc_mean, rc_std, nsrc, photometry=photometry)
     radec = am.radec_line(koaid, res)
     with open(directory + 'epoch_grand_pasep', 'a') as f:               # :529-533
         f.write(pasep + "\n")
