@@ -4,7 +4,9 @@ position angle / RA / Dec of b and c about a, on the GPU, with --corner the corn
 plot's histograms and quantile brackets, with --residuals the posterior's model and
 residual images, with --autocorr the chains' autocorrelation times and effective sample
 sizes, and with --photometry the companions' flux ratios and delta magnitudes, the FWHM and
-the sources' S/N; see olpefit_amd/step3.py).
+the sources' S/N, and with --covariance the parameter covariance, the error ellipses of b
+and c about a, the conditional widths and the multivariate Gelman-Rubin statistic; see
+olpefit_amd/step3.py).
 
     python 3body/apf_step3_3body.py <image> <system> -s <walkers> [-a <burn>]
         [--astrometry [--distortion X.fits Y.fits] [--delta-r MAS] [--prepost pre|post]]
@@ -12,6 +14,7 @@ the sources' S/N; see olpefit_amd/step3.py).
         [--residuals [--residuals-thin N] [--bkgd-mode 0|1]]
         [--autocorr [--autocorr-max-lag N] [--autocorr-c X]]
         [--photometry [--photometry-thin N]]
+        [--covariance [--covariance-thin N]]
 """
 import os
 import sys

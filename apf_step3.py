@@ -10,7 +10,10 @@ per parameter, the lag sums folded on the GPU and written to <frame>_autocorr.np
 --photometry the companion's flux ratio and delta magnitude, the primary's flux, the FWHM and
 the core fraction of every chain row, reduced on the GPU, and the reference's aperture S/N and
 FWHM numbers, written to <frame>_photometry.npz and, with --astrometry, into the S/N and FWHM
-fields of the epoch_grand_pasep line (nothing is drawn).
+fields of the epoch_grand_pasep line; with --covariance the parameter covariance and
+correlations, the companion's error ellipse, the conditional widths and the multivariate
+Gelman-Rubin statistic, the cross-column sums folded on the GPU and written to
+<frame>_covariance.npz (nothing is drawn).
 
     python apf_step3.py <dir>/N2.<date>.<frame>.LDIF.fits <system> -s <walkers> [-a <burn>]
         [--astrometry [--distortion X.fits Y.fits] [--delta-r MAS] [--prepost pre|post]]
@@ -18,6 +21,7 @@ fields of the epoch_grand_pasep line (nothing is drawn).
         [--residuals [--residuals-thin N] [--bkgd-mode 0|1]]
         [--autocorr [--autocorr-max-lag N] [--autocorr-c X]]
         [--photometry [--photometry-thin N]]
+        [--covariance [--covariance-thin N]]
 """
 import os
 import sys

@@ -594,6 +594,81 @@ int olpe_phot_samples(olpe_phot *p, int plane, double *out);
  * folded last may be folded again. */
 int olpe_phot_reset(olpe_phot *p);
 
+/* --- parameter covariance: the cross-column sums (apf_step3.py:603-643) -----------------
+ * The reference's corner figure (apf_step3.py:603-643) shows every pair of columns as a
+ * scatter and gives no number for it.  An olpe_cov holds what every two-column question is
+ * a function of: about a fixed pivot p [ncols], with d = x - p per row,
+ *     n, skipped      rows folded and rows left out
+ *     S1[j]    = sum d_j
+ *     S2[j][k] = sum d_j d_k      the full symmetric matrix, its triangles bit-equal
+ * and, created with walkers > 0, per walker w its row count nw[w] and S1w[w][j] = its sum of
+ * d_j.  A row with a non-finite value in any column is left out whole and counted once: it
+ * enters no sum and no nw.  mean = p + S1 / n, cov = (S2 - S1 S1^T / n) / (n - 1); the
+ * correlation, the error ellipse, the conditional widths and the multivariate Gelman-Rubin
+ * statistic are host arithmetic on the state (olpefit_amd/covariance.py).
+ * The pivot: given at create, or set on the device by the first fold from its first row
+ * (walker 0, row 0; a non-finite entry becomes 0.0); it then stays fixed until reset.  An
+ * unlucky pivot costs precision, not correctness: the relative error of a variance read
+ * from the sums grows as 1 + (mean - p)^2 / sigma^2.
+ * No floating-point atomics: every sum runs in an order fixed by the fold's shape (per
+ * workgroup partial sums over fixed runs of 256-row tiles, then one fixed tree), so the
+ * same fold of the same rows gives the same bits whatever the device or grid.  The state is
+ * additive over folds, objects, ranks and checkpoints whose pivots are bit-equal.  An
+ * olpe_cov belongs to a device, not to a sampler context.  Calls on one object are not
+ * thread-safe.  Not covered: per-walker covariance matrices, sky-frame ellipses, a
+ * collective over the state. */
+typedef struct olpe_cov olpe_cov;
+/* The set-up of apf_step3.py:603-643's pair sums: 1 <= ncols <= 24; walkers 0 (pooled sums
+ * only) or the ensemble's walker count, at most 65535 x 64; pivot [ncols], all finite, or
+ * NULL (the first fold sets it).  Anything else is OLPE_EINVAL, naming the value, before
+ * any GPU call; a per-walker store the device cannot hold is OLPE_ENOMEM naming its bytes.
+ * OLPE_COV_TILE=64|128|256 sets the fold kernel's rows per tile (a test knob, 256 by
+ * default: results agree to rounding, not to the bit, across tiles). */
+int olpe_cov_create(int device, int ncols, long long walkers, const double *pivot,
+                    olpe_cov **out);
+/* Frees the object of apf_step3.py:603-643's pair sums (waits for its folds in flight). */
+void olpe_cov_destroy(olpe_cov *h);
+/* The sums (apf_step3.py:603-643's pairs) for rows 0, row_step, 2 row_step, ... of every
+ * walker of ctx's last launch, read from its device chain in place (async on the context's
+ * stream, no host copy; ncols == PS).  Once per launch: OLPE_ESTATE if this launch was
+ * folded already; OLPE_EINVAL for row_step < 1, for a context of another device or PS, and,
+ * with walkers > 0, of another walker count. */
+int olpe_cov_fold_ctx(olpe_cov *h, olpe_ctx *ctx, int row_step);
+/* The same sums (apf_step3.py:603-643's pairs) for host rows, walker-major
+ * [nwalkers][nrows][ncols] (time_major 0) or time-major [nrows][nwalkers][ncols] (1, step
+ * 3's chains), uploaded as they lie (no transposition) in pieces of at most 256 MiB.  With
+ * walkers > 0 nwalkers must equal it; with walkers 0 the first two dimensions are just
+ * rows.  A fold that fits one piece runs the kernels of olpe_cov_fold_ctx on the same
+ * layout: a launch's chain read back and folded here gives that fold's bits. */
+int olpe_cov_fold_rows(olpe_cov *h, const double *rows, long long nwalkers, long long nrows,
+                       int time_major);
+/* The pooled state so far (apf_step3.py:603-643's pairs summed): *n, *skipped, *has_pivot
+ * (0 until a pivot is given or set), pivot [ncols] (zeros while there is none), S1 [ncols],
+ * S2 [ncols][ncols]; any may be NULL.  Waits for the folds in flight. */
+int olpe_cov_get(olpe_cov *h, unsigned long long *n, unsigned long long *skipped,
+                 int *has_pivot, double *pivot, double *S1, double *S2);
+/* The walkers' part of the state (apf_step3.py:169-205's chains, one per walker): nw
+ * [walkers], S1w [walkers][ncols]; either may be NULL.  OLPE_ESTATE for an object created
+ * with walkers 0.  Waits for the folds in flight. */
+int olpe_cov_walkers_get(olpe_cov *h, unsigned long long *nw, double *S1w);
+/* The between-walker term of the multivariate Gelman-Rubin statistic over
+ * apf_step3.py:169-205's chains, reduced on the device in a fixed order: B [ncols][ncols]
+ * = sum over the walkers with nw > 0 of S1w[w][j] S1w[w][k] / nw[w] (both triangles, bit-
+ * equal), *m the number of such walkers, *nw_min and *nw_max the extremes of their counts (0
+ * with no such walker); any may be NULL.  OLPE_ESTATE for an object created with walkers 0. */
+int olpe_cov_between(olpe_cov *h, double *B, unsigned long long *m, unsigned long long *nw_min,
+                     unsigned long long *nw_max);
+/* Adds another object's, rank's or checkpoint's state (apf_step3.py:603-643's pairs over
+ * the union of their rows); nw and S1w are read with walkers > 0 only.  OLPE_EINVAL, naming
+ * which differs, if its ncols, its walkers or any bit of its pivot differ (the state is then
+ * untouched); an object without a pivot yet adopts the incoming one. */
+int olpe_cov_add(olpe_cov *h, int ncols, long long walkers, unsigned long long n,
+                 unsigned long long skipped, const double *pivot, const double *S1,
+                 const double *S2, const unsigned long long *nw, const double *S1w);
+/* Zeroes the state (apf_step3.py:603-643 starts over); a pivot given at create stays, an
+ * automatic one is forgotten; the launch folded last may be folded again. */
+int olpe_cov_reset(olpe_cov *h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,6 +125,16 @@ SIGNATURES = {
     "olpe_phot_finalize": (_i, [_P, _pd, _i, _pd]),
     "olpe_phot_samples": (_i, [_P, _i, _pd]),
     "olpe_phot_reset": (_i, [_P]),
+    "olpe_cov_create": (_i, [_i, _i, _ll, _pd, C.POINTER(_P)]),
+    "olpe_cov_destroy": (None, [_P]),
+    "olpe_cov_fold_ctx": (_i, [_P, _P, _i]),
+    "olpe_cov_fold_rows": (_i, [_P, _pd, _ll, _ll, _i]),
+    "olpe_cov_get": (_i, [_P, _pu64, _pu64, C.POINTER(_i), _pd, _pd, _pd]),
+    "olpe_cov_walkers_get": (_i, [_P, _pu64, _pd]),
+    "olpe_cov_between": (_i, [_P, _pd, _pu64, _pu64, _pu64]),
+    "olpe_cov_add": (_i, [_P, _i, _ll, C.c_ulonglong, C.c_ulonglong, _pd, _pd, _pd, _pu64,
+                          _pd]),
+    "olpe_cov_reset": (_i, [_P]),
     "olpe_moments_fault": (_i, [_P, _i]),
     "olpe_test_hold_handoff": (_i, [_P, _i]),
 }

@@ -184,7 +184,9 @@ def main(argv=None, nsrc: int = 2):
     ``--corner`` and ``--residuals`` add the corner plot's counts and the posterior's model
     / residual images (``corner``, ``residuals`` below) in the same way, ``--autocorr`` the
     chains' integrated autocorrelation times and effective sample sizes (``autocorr``),
-    ``--photometry`` the flux ratio, delta magnitude, FWHM and S/N (``photometry``)."""
+    ``--photometry`` the flux ratio, delta magnitude, FWHM and S/N (``photometry``),
+    ``--covariance`` the parameter covariance, the companions' error ellipses, the conditional
+    widths and the multivariate Gelman-Rubin statistic (``covariance``)."""
     import argparse
     import json
     import sys
@@ -243,6 +245,13 @@ def main(argv=None, nsrc: int = 2):
                          "FWHM fields of the epoch_grand_pasep line")
     ap.add_argument("--photometry-thin", type=int, default=1, metavar="N",
                     help="fold every N-th row after the burn-in")
+    ap.add_argument("--covariance", action="store_true",
+                    help="parameter covariance and correlations, the companions' error "
+                         "ellipses (detector frame), conditional widths and the multivariate "
+                         "Gelman-Rubin statistic of the chains (GPU); writes "
+                         "<frame>_covariance.npz")
+    ap.add_argument("--covariance-thin", type=int, default=1, metavar="N",
+                    help="fold every N-th row after the burn-in")
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
     say = (lambda *a: None) if args.quiet else print
     ncor = int(np.int_(args.size))                                  # :76-77
@@ -254,6 +263,11 @@ def main(argv=None, nsrc: int = 2):
         # burn-in cannot be taken out of them afterwards
         ap.error(f"--from-moments covers every recorded row (additional_burnin 1); "
                  f"-a {additional_burnin} needs the chain files")
+    if args.from_moments and args.covariance:
+        ap.error("--covariance needs the chain rows (per-column moments hold no cross "
+                 "terms): drop --from-moments")
+    if args.covariance and args.covariance_thin < 1:
+        ap.error(f"--covariance-thin {args.covariance_thin}: must be >= 1")
     for flag, why in (("astrometry", "a median is not a moment"),
                       ("corner", "a histogram is not a moment"),
                       ("residuals", "moments are not samples"),
@@ -325,6 +339,8 @@ def main(argv=None, nsrc: int = 2):
         out["autocorr"] = autocorr(args, chains, nsrc, input_directory, say)
     if phot:
         out["photometry"] = phot
+    if args.covariance:
+        out["covariance"] = covariance(args, chains, nsrc, stats, input_directory, say)
     with open(input_directory + "step3_summary.json", "w") as f:
         json.dump(out, f, indent=1)
     return out
@@ -364,6 +380,60 @@ def autocorr(args, chains, nsrc, input_directory, say=print):
                                "suggested_stride": int(res["suggested_stride"][k]),
                                "note": res["notes"][k]}
                         for k, name in enumerate(labels)}}
+
+
+def covariance(args, chains, nsrc, stats, input_directory, say=print):
+    """What the per-column statistics above cannot say (the reference's corner figure,
+    apf_step3.py:603-643, shows the pair scatter and gives no number for it): the covariance
+    and correlation matrix of the chains [N, M, PS] already read, the error ellipse of each
+    companion's offset from the primary (detector frame; pixscale the header's, as
+    ``photometry`` takes it), each parameter's conditional width given all the others, and
+    Brooks & Gelman's multivariate R-hat over the walkers.  The cross-column sums are folded
+    on the GPU (covariance.Covariance) from every ``--covariance-thin``-th row as the rows
+    lie (time-major), one walker per chain file, about the column means just computed.  The
+    conditional widths and R-hat run over the parameters; chi^2 is left out.  Writes
+    ``<frame>_covariance.npz`` beside the chain files and returns what
+    ``step3_summary.json`` records."""
+    from . import astrometry as am, covariance as cv, fitsio
+    labels = NAMES_2 if nsrc == 2 else NAMES_3
+    _, hdr = fitsio.getdata_header(args.image)
+    prepost = resolve_prepost(args)
+    pixscale = am.header_scalars(hdr, prepost)["pixscale"]
+    say('Computing parameter covariance...')
+    thinned = chains[::args.covariance_thin]
+    # the pivot: the column means (chi^2's, which summary leaves out, from the rows folded)
+    pivot = np.array([stats[k]["mean"] for k in labels[:-1]]
+                     + [float(np.mean(thinned[..., -1]))])
+    pivot = np.where(np.isfinite(pivot), pivot, 0.0)
+    path = results_prefix(args, input_directory) + '_covariance.npz'
+    with cv.Covariance(chains.shape[2], walkers=chains.shape[1], pivot=pivot,
+                       labels=labels) as c:
+        c.fold_rows(thinned, time_major=True)
+        st, res = c.save(path, nsrc=nsrc, pixscale=pixscale,
+                         param_cols=range(chains.shape[2] - 1))
+    for line in cv.table_lines(res):
+        say(line)
+
+    def num(v):                                   # JSON has no NaN
+        return float(v) if v is not None and np.isfinite(v) else None
+    cs, mp = res["conditional"], res["mpsrf"]
+    return {"file": path, "thin": args.covariance_thin, "prepost": prepost,
+            "pixscale": pixscale, "n": st["n"], "skipped": st["skipped"],
+            "walkers": st["walkers"],
+            "largest_correlations": [{"a": a, "b": b, "r": num(r)} for a, b, r in res["pairs"]],
+            "ellipses": {e["name"]: {"semi_major_px": num(e["semi_major"]),
+                                     "semi_minor_px": num(e["semi_minor"]),
+                                     "semi_major_mas": num(e["semi_major_mas"]),
+                                     "semi_minor_mas": num(e["semi_minor_mas"]),
+                                     "angle_deg": num(e["angle"]), "rho": num(e["rho"])}
+                         for e in res["ellipses"]},
+            "condition": num(cs["condition"]),
+            "columns": {labels[k]: {"sigma": num(cs["sigma_marginal"][i]),
+                                    "sigma_conditional": num(cs["sigma_cond"][i]),
+                                    "efficiency": num(cs["efficiency"][i]),
+                                    "rhat": num(mp["rhat"][i]), "note": res["notes"][k]}
+                        for i, k in enumerate(cs["cols"])},
+            "mpsrf": num(mp["mpsrf"]), "mpsrf_note": mp["note"]}
 
 
 def corner(args, chains, nsrc, input_directory, say=print):
