@@ -31,6 +31,13 @@ int olpe_moments_fault(olpe_ctx *ctx, int where);
  * not all be resident (too many walkers for the device). */
 int olpe_test_hold_handoff(olpe_ctx *ctx, int on);
 
+/* Upload chain[W][nrec][PS] into the context's device chain buffer as if a sampler launch
+ * had just recorded it: grows the buffer as olpe_run does, sets the launch's row count,
+ * counts one launch (so olpe_moments_accumulate and every *_fold_ctx accept it), records
+ * the launch's two events on the stream.  The iteration count, state, RNG and counters are
+ * untouched.  nrec may be 0.  OLPE_ESTATE before olpe_seed. */
+int olpe_test_chain_set(olpe_ctx *ctx, const double *chain, long long nrec);
+
 #ifdef __cplusplus
 }
 #endif

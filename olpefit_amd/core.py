@@ -340,6 +340,17 @@ class Sampler:
         wait happens by construction (olpe_unit_stats counts it)."""
         check(self._lib.olpe_test_hold_handoff(self._ctx, 1 if on else 0))
 
+    def test_chain_set(self, chain):
+        """Test hook (olpe_test_chain_set, include/olpe_test.h): chain [W, nrec, PS]
+        becomes the device chain as if a sampler launch had just recorded it (one launch
+        counted; iteration count, state, RNG and counters untouched).  nrec may be 0."""
+        ch = np.ascontiguousarray(chain, dtype=np.float64)
+        if ch.ndim != 3 or ch.shape[2] != self.ps or (self.W and ch.shape[0] != self.W):
+            raise ValueError(f"chain must be [{self.W}, nrec, {self.ps}]")   # (W = 0: unseeded)
+        check(self._lib.olpe_test_chain_set(self._ctx, _dptr(ch), ch.shape[1]))
+        self._nrec = int(ch.shape[1])
+        self._record_stride = 1
+
     def moments_fault(self, where: int):
         """Test hook (olpe_moments_fault, include/olpe_test.h): 1 = the summary's
         allocation fails, 2 = its launch fails after the uniformity check, 3 = the check

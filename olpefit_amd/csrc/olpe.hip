@@ -1648,6 +1648,30 @@ int olpe_test_hold_handoff(olpe_ctx *c, int on) {
   return OLPE_OK;
 }
 
+int olpe_test_chain_set(olpe_ctx *c, const double *chain, long long nrec) {
+  if (!c || nrec < 0 || (nrec > 0 && !chain)) return set_err(OLPE_EINVAL, "bad argument");
+  if (!c->d_state || !c->seeded) return set_err(OLPE_ESTATE, "call olpe_seed first");
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));   // a queued fold may still read the old rows
+  int rc;
+  const size_t chain_need = (size_t)c->W * nrec * c->ps;
+  if (chain_need > c->chain_cap) {
+    c->chain_cap = 0;
+    if ((rc = dev_alloc(&c->d_chain, chain_need))) return rc;
+    c->chain_cap = chain_need;
+  }
+  hipEvent_t *ev = c->ev[c->launches % olpe_ctx::kRing];
+  if (!ev[0] || !ev[1]) return set_err(OLPE_EHIP, "launch events were not created");
+  HIPCHK(hipEventRecord(ev[0], c->stream));
+  if (chain_need)
+    HIPCHK(hipMemcpyAsync(c->d_chain, chain, chain_need * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipEventRecord(ev[1], c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));   // the caller's buffer is free on return
+  c->chain_rows = nrec;
+  ++c->launches;
+  return OLPE_OK;
+}
+
 int olpe_trace_enable(olpe_ctx *c, int on) {
   if (!c) return set_err(OLPE_EINVAL, "NULL ctx");
   c->trace_on = on != 0;

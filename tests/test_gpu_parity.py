@@ -1296,6 +1296,9 @@ def test_moments_fold_matches_numpy(golden, lib_loaded):
     # squared otherwise: absolute slack n (10 eps |mean|)^2
     slack = n * (10 * np.finfo(float).eps * np.abs(ref_mean)) ** 2
     assert np.all(np.abs(m2 - ref_m2) <= 1e-10 * np.abs(ref_m2) + slack)
+    # and within the derived bounds of the long-double reference, unchanged columns exact
+    import moments_restatement as mr
+    print("mean, M2 err / bound:", mr.check(n, mean, m2, chain))
     centre = ref_mean.mean(axis=0)
     summ = s.moments_summary(centre)
     ps, np_ = s.ps, s.np_
@@ -1351,4 +1354,6 @@ def test_moments_fold_long_launches(golden, lib_loaded, name):
     np.testing.assert_allclose(mean, ref_mean, rtol=1e-13)
     slack = nrow * (10 * np.finfo(float).eps * np.abs(ref_mean)) ** 2
     assert np.all(np.abs(m2 - ref_m2) <= 1e-10 * np.abs(ref_m2) + slack)
+    import moments_restatement as mr
+    print("mean, M2 err / bound:", mr.check(nrow, mean, m2, chain))
 
