@@ -110,7 +110,8 @@ template <int NP> struct WaveSlice {
   static constexpr int U32 = 2 * NP;                         // 8-byte multiple for NP 16/19
   static constexpr int PS = NP + 1;
   static constexpr int NSRC = NP == 16 ? 2 : 3;
-  // doubles: params[PS] | T1[5] T2[5] | C1[3] C2[3] | pending T[5] C[3] | proposal[PS];
+  // doubles: params[PS] | T1[5] T2[5] | C1[3] C2[3] | pending T[5] C[3] | PS unused (OPR:
+  // the proposal vector of the per-step descriptor rebuild, gone with it);
   // a shape set's T holds cos^2, sin^2, sin 2theta and (FAST) 1/sigma_x^2, 1/sigma_y^2
   static constexpr int OT1 = PS, OT2 = PS + 5, OC1 = PS + 10, OC2 = PS + 13;
   static constexpr int OPT = PS + 16, OPC = PS + 21;
@@ -426,11 +427,25 @@ void olpe_gibbs_kernel(GibbsArgs A) {
     wave_sync();
     if (lane == 0) {
       const Trig t1 = make_trig<FAST>(st[L::T1]), t2 = make_trig<FAST>(st[L::T2]);
-      st_shape(st + WS::OT1, t1, inv_var(st[L::S1X]), inv_var(st[L::S1Y]));
-      st_shape(st + WS::OT2, t2, inv_var(st[L::S2X]), inv_var(st[L::S2Y]));
-      st_coef(st + WS::OC1, make_coef<FAST>(st[L::S1X], st[L::S1Y], t1));
-      st_coef(st + WS::OC2, make_coef<FAST>(st[L::S2X], st[L::S2Y], t2));
+      // (the four reciprocal variances once: make_coef<true> is coef_inv of the same)
+      const double i1x = inv_var(st[L::S1X]), i1y = inv_var(st[L::S1Y]);
+      const double i2x = inv_var(st[L::S2X]), i2y = inv_var(st[L::S2Y]);
+      st_shape(st + WS::OT1, t1, i1x, i1y);
+      st_shape(st + WS::OT2, t2, i2x, i2y);
+      if constexpr (FAST) {
+        st_coef(st + WS::OC1, coef_inv(t1, i1x, i1y));
+        st_coef(st + WS::OC2, coef_inv(t2, i2x, i2y));
+      } else {
+        st_coef(st + WS::OC1, make_coef<FAST>(st[L::S1X], st[L::S1Y], t1));
+        st_coef(st + WS::OC2, make_coef<FAST>(st[L::S2X], st[L::S2Y], t2));
+      }
     }
+    wave_sync();
+    // the descriptor of the walker's state: the loop below keeps it by patching the
+    // fields a draw feeds and patching them back after a reject (patch_desc)
+    const int bg_idx = A.bkgd_mode == 0 ? L::BG_QUIRK : L::BG_FIXED;
+    build_desc<NSRC, NT, FAST>(mdl, colc, [&](int k) -> double { return st[k]; },
+                               ld_coef(st + WS::OC1), ld_coef(st + WS::OC2), bg_idx, lane, etab);
     wave_sync();
 
     MTWave mt;
@@ -557,38 +572,28 @@ void olpe_gibbs_kernel(GibbsArgs A) {
         if (lane == 0) st_coef(st + WS::OPC, C);
         return C;
       };
-      Coef C1p, C2p;
-      if (grp == 1) C1p = set_coef(WS::OT1, L::S1X, L::S1Y, L::T1);
-      else C1p = ld_coef(st + WS::OC1);
-      if (grp == 2) C2p = set_coef(WS::OT2, L::S2X, L::S2Y, L::T2);
-      else C2p = ld_coef(st + WS::OC2);
-      // the step's model descriptor goes to LDS (the sweep loads each field where it is
-      // used instead of holding 6*G doubles in registers across it), built lane-parallel:
-      // lane g < G writes Gaussian g with make_model's operations, lane G the background
-      // the proposal vector, lane-parallel, so that the descriptor lanes read their
-      // fields without a per-field select against the drawn index
-      if (lane < PS) st[WS::OPR + lane] = (lane == r) ? nv : st[lane];
-      wave_sync();
-      if (lane < 2 * NSRC) {
-        const int s = lane >> 1;
-        const bool narrow = lane & 1;
-        auto ql = [&](int k) -> double { return st[WS::OPR + k]; };
-        const double tot = ql(L::sa(s)) - ql(L::OFF);
-        const double wide = tot * ql(L::RATIO);
-        const double xc = ql(L::sx(s)), yc = ql(L::sy(s));
-        // component-wise selects (a select of whole structs goes through scratch)
-        const Coef C{narrow ? C1p.a : C2p.a, narrow ? C1p.b : C2p.b, narrow ? C1p.c : C2p.c};
-        const double dx = narrow ? 0.0 : ql(L::DX), dy = narrow ? 0.0 : ql(L::DY);
-        const Gauss gq{narrow ? tot - wide : wide, narrow ? xc : xc + dx,
-                       narrow ? yc : yc + dy, C};
-        mdl->g[lane] = gq;
-        // FAST sweeps of n = 64 / 128: the column-term coefficients of this Gaussian
-        // (col_term64, row group 0 and S = 1 in both)
-        if constexpr (FAST && NT >= 64) col_coef(gq, (double)(NT / 2), colc + 3 * lane);
-        // (two column passes: rho of pass 1 = rho of pass 0 x exp(-64 b), pass_rho)
-        if constexpr (FAST && NT == 128) colc[6 * NSRC + lane] = ExpTab{etab}(-64.0 * gq.k.b);
-      } else if (lane == 2 * NSRC) {
-        mdl->bg = q(A.bkgd_mode == 0 ? L::BG_QUIRK : L::BG_FIXED);
+      Coef Cp{0.0, 0.0, 0.0};
+      if (grp == 1) Cp = set_coef(WS::OT1, L::S1X, L::S1Y, L::T1);
+      if (grp == 2) Cp = set_coef(WS::OT2, L::S2X, L::S2Y, L::T2);
+      // The model descriptor lives in LDS (the sweep loads each field where it is used
+      // instead of holding 6*G doubles in registers across it) and describes the current
+      // state between iterations: the draw rewrites the fields that parameter r feeds,
+      // for the proposal here and, after a reject, for the state again below.
+      // A NaN proposal (logproposal of a value <= 0, apf_step2.py:66-69: a background
+      // guessed below 0 proposes NaN at every draw of it) makes the reference's model NaN
+      // at every pixel, its masked chi^2 NaN and the step a reject (:134-148): no sweep
+      // (the guards would send it to the exact sweep, and in the ring sampler hold up
+      // the workgroup), the descriptor and the caches left as they are.
+      // (an int: a uniform bool carried across the sweep is kept as a lane mask)
+      const int nan_prop = __builtin_amdgcn_readfirstlane((int)!(nv == nv));
+      if (!nan_prop) {
+        // (the lane laundered at both patches: the descriptor lanes' addresses and
+        // selects are formed where they are used, not hoisted out of the sampler loop
+        // and held in VGPRs across the sweep)
+        int pl = lane;
+        asm volatile("" : "+v"(pl));
+        patch_desc<NSRC, NT, FAST>(mdl, colc, st, r, nv, Cp, grp,
+                                   A.bkgd_mode == 0 ? L::BG_QUIRK : L::BG_FIXED, pl, etab);
       }
       wave_sync();
 
@@ -618,12 +623,7 @@ void olpe_gibbs_kernel(GibbsArgs A) {
       // (per-column guard cache: the Gaussians this draw moves or reshapes -- a shape
       // set is the narrow Gaussians, odd g, or the wide ones, even g)
       gcache.changed = gmask | ((grp == 1 ? 0xAAAu : grp == 2 ? 0x555u : 0u) & ((1u << (2 * NSRC)) - 1u));
-      // A NaN proposal (logproposal of a value <= 0, apf_step2.py:66-69: a background
-      // guessed below 0 proposes NaN at every draw of it) makes the reference's model NaN
-      // at every pixel, its masked chi^2 NaN and the step a reject (:134-148): no sweep
-      // (the guards would send it to the exact sweep, and in the ring sampler hold up
-      // the workgroup), the caches left as they are.
-      const bool nan_prop = !(nv == nv);
+      // (a NaN proposal, above: no sweep)
       double part;
       if (nan_prop) {
         gcache.same = false;
@@ -667,6 +667,16 @@ void olpe_gibbs_kernel(GibbsArgs A) {
       if constexpr (FAST && NT != 0 && NT <= 64) {
         if (acc && gmask) colcache_accept<NSRC, NT>(ccache, *mdl, gmask, lane, etab);
         ccache.pend = 0;              // parked terms belong to this step only
+      }
+      // a reject: the patched fields return to the state's values, bit for bit (the same
+      // function of the state's parameter and its shape set's cached coefficients)
+      if (!acc && !nan_prop) {
+        Coef Cs{0.0, 0.0, 0.0};
+        if (grp) Cs = ld_coef(st + (grp == 1 ? WS::OC1 : WS::OC2));
+        int pl = lane;
+        asm volatile("" : "+v"(pl));
+        patch_desc<NSRC, NT, FAST>(mdl, colc, st, r, st[r], Cs, grp,
+                                   A.bkgd_mode == 0 ? L::BG_QUIRK : L::BG_FIXED, pl, etab);
       }
       wave_sync();
       if (acc && lane == 0) {

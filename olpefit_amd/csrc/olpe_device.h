@@ -1151,7 +1151,9 @@ __device__ __forceinline__ bool fast3_amp_ok(const ModelDesc<NSRC> &m, int lane,
 // in registers; with the interleaved layout and an 8-byte read per row that sweep ran
 // level with two 16-byte reads per row, with this one +2.8 %: profiles/r07/ab_htab_dpp.log).
 __host__ __device__ constexpr bool htab_split(int nt) { return nt == 64; }
-template <int NSRC, bool SPLIT = false>
+// INPLACE (tab == from, the single-slot sampler): a set not in `which` is left alone
+// instead of being read and written back.
+template <int NSRC, bool SPLIT = false, bool INPLACE = false>
 __device__ __forceinline__ void build_htab(const ModelDesc<NSRC> &m, double *tab,
                                            const double *from, int which, int rows, int kc,
                                            double S, int lane, ExpTab ex) {
@@ -1160,6 +1162,11 @@ __device__ __forceinline__ void build_htab(const ModelDesc<NSRC> &m, double *tab
   for (int k = lane; k < rows; k += 64) {
     const double dk = (double)(k - kc);
     const double e = dk * (dk - 1.0);
+    if constexpr (INPLACE) {
+      if (which & 1) tab[SPLIT ? k : 2 * k] = ex(-(cw2 * e));
+      if (which & 2) tab[SPLIT ? rows + k : 2 * k + 1] = ex(-(cn2 * e));
+      continue;
+    }
     double2 h;
     h.x = (which & 1) ? ex(-(cw2 * e)) : from[SPLIT ? k : 2 * k];
     h.y = (which & 2) ? ex(-(cn2 * e)) : from[SPLIT ? rows + k : 2 * k + 1];
@@ -1287,6 +1294,135 @@ template <int NSRC> __device__ __forceinline__ unsigned gauss_mask(int r) {
     if (r == L::S1X || r == L::S1Y || r == L::T1) msk |= 2u << (2 * s);
   }
   return msk;
+}
+
+// The sampler's model descriptor in LDS (*mdl, and colc: col_coef [G][3], then at
+// 128 x 128 the pass-step factors exp(-64 b) [G]).  Between Gibbs iterations it describes
+// the walker's current state; a draw rewrites only the fields its parameter feeds
+// (patch_desc) and a rejected draw rewrites them from the state.  Every field is the
+// same pure function of the parameters whichever of the two writes it, with
+// make_model's operations and operand order:
+//   amp   <- sa(s), OFF, RATIO          x0 <- sx(s), DX (wide)      y0 <- sy(s), DY (wide)
+//   k     <- the Gaussian's shape set (narrow C1, wide C2)
+//   colc  <- y0, k.b, k.c  (FAST, n >= 64)      pass factor <- k.b  (FAST, n = 128)
+//   bg    <- BG_QUIRK (bkgd_mode 0: a shape parameter of the 2-source layout) or BG_FIXED
+template <int NSRC> struct DescDeps {
+  using L = Layout<NSRC>;
+  // bit k = parameter k is a per-source amplitude (0), x (1) or y (2)
+  __host__ __device__ static constexpr unsigned per_source(int what) {
+    unsigned m = 0;
+    for (int s = 0; s < NSRC; ++s)
+      m |= 1u << (what == 0 ? L::sa(s) : what == 1 ? L::sx(s) : L::sy(s));
+    return m;
+  }
+  static constexpr unsigned AMP = per_source(0) | (1u << L::OFF) | (1u << L::RATIO);
+  static constexpr unsigned X = per_source(1) | (1u << L::DX);
+  static constexpr unsigned Y = per_source(2) | (1u << L::DY);
+};
+
+// column-term coefficients (and the 128 x 128 pass factor) of descriptor lane `lane`
+template <int NSRC, int NT, bool FAST>
+__device__ __forceinline__ void desc_colc(double *colc, int lane, double y0, double b, double c,
+                                          bool with_pass, const double *etab) {
+  if constexpr (FAST && NT >= 64) {
+    Gauss gq;
+    gq.y0 = y0;
+    gq.k.b = b;
+    gq.k.c = c;
+    col_coef(gq, (double)(NT / 2), colc + 3 * lane);
+    // (two column passes: rho of pass 1 = rho of pass 0 x exp(-64 b), pass_rho)
+    if constexpr (NT == 128) {
+      if (with_pass) colc[6 * NSRC + lane] = ExpTab{etab}(-64.0 * b);
+    }
+  }
+}
+
+// The whole descriptor of the parameter vector q (an accessor), lane-parallel: lane
+// g < G writes Gaussian g, lane G the background (once per work unit, from the state)
+template <int NSRC, int NT, bool FAST, class Q>
+__device__ __forceinline__ void build_desc(ModelDesc<NSRC> *mdl, double *colc, const Q &ql,
+                                           const Coef &C1, const Coef &C2, int bg_idx, int lane,
+                                           const double *etab) {
+  using L = Layout<NSRC>;
+  if (lane < 2 * NSRC) {
+    const int s = lane >> 1;
+    const bool narrow = lane & 1;
+    const double tot = ql(L::sa(s)) - ql(L::OFF);
+    const double wide = tot * ql(L::RATIO);
+    const double xc = ql(L::sx(s)), yc = ql(L::sy(s));
+    // component-wise selects (a select of whole structs goes through scratch)
+    const Coef C{narrow ? C1.a : C2.a, narrow ? C1.b : C2.b, narrow ? C1.c : C2.c};
+    const double dx = narrow ? 0.0 : ql(L::DX), dy = narrow ? 0.0 : ql(L::DY);
+    const Gauss gq{narrow ? tot - wide : wide, narrow ? xc : xc + dx,
+                   narrow ? yc : yc + dy, C};
+    mdl->g[lane] = gq;
+    desc_colc<NSRC, NT, FAST>(colc, lane, gq.y0, gq.k.b, gq.k.c, true, etab);
+  } else if (lane == 2 * NSRC) {
+    mdl->bg = ql(bg_idx);
+  }
+}
+
+// The fields that parameter r feeds, for the parameter vector {state with p[r] = v}:
+// one wave-uniform branch per class of r (r is a scalar), the descriptor lanes doing
+// build_desc's operations for those fields only.  C = the coefficients of r's shape set
+// (grp 1 narrow, 2 wide; unused for grp 0).  Lanes whose Gaussian r does not feed rewrite
+// the value they hold (the same function of the same inputs).  The caller syncs the wave.
+template <int NSRC, int NT, bool FAST>
+__device__ __forceinline__ void patch_desc(ModelDesc<NSRC> *mdl, double *colc, const double *st,
+                                           int r, double v, const Coef &C, int grp, int bg_idx,
+                                           int lane, const double *etab) {
+  using L = Layout<NSRC>;
+  using D = DescDeps<NSRC>;
+  const bool dl = lane < 2 * NSRC;
+  const int s = lane >> 1;
+  const bool narrow = lane & 1;
+  // FAST: the compiler reads a parameter behind a branch on r (the drawn one is not
+  // loaded): fewer VALU instructions, which is what the FAST step's time follows.
+  // EXACT: a lane-varying zero the compiler cannot see through keeps the reads loads and
+  // selects, issued together; with the branches the EXACT samplers ran 0.1-0.9 % slower
+  // (profiles/r12/README.md).  The values are the same.
+  int z = 0;
+  if constexpr (!FAST) asm volatile("" : "+v"(z));
+  auto q = [&](int k) -> double {
+    if constexpr (FAST) {
+      return (k == r) ? v : st[k];
+    } else {
+      const double cur = st[k + z];
+      return (k + z == r) ? v : cur;
+    }
+  };
+  if ((D::AMP >> r) & 1u) {
+    if (dl) {
+      const double tot = q(L::sa(s)) - q(L::OFF);
+      const double wide = tot * q(L::RATIO);
+      mdl->g[lane].amp = narrow ? tot - wide : wide;
+    }
+  } else if ((D::X >> r) & 1u) {
+    if (dl) {
+      const double xc = q(L::sx(s));
+      const double dx = narrow ? 0.0 : q(L::DX);
+      mdl->g[lane].x0 = narrow ? xc : xc + dx;
+    }
+  } else if ((D::Y >> r) & 1u) {
+    if (dl) {
+      const double yc = q(L::sy(s));
+      const double dy = narrow ? 0.0 : q(L::DY);
+      const double y0 = narrow ? yc : yc + dy;
+      mdl->g[lane].y0 = y0;
+      // (the pass factor depends on the shape alone)
+      if constexpr (FAST && NT >= 64)
+        desc_colc<NSRC, NT, FAST>(colc, lane, y0, mdl->g[lane].k.b, mdl->g[lane].k.c, false, etab);
+    }
+  } else if (grp) {
+    if (dl && narrow == (grp == 1)) {
+      mdl->g[lane].k = C;
+      if constexpr (FAST && NT >= 64)
+        desc_colc<NSRC, NT, FAST>(colc, lane, mdl->g[lane].y0, C.b, C.c, true, etab);
+    }
+  }
+  // (the background is one of the parameters above in either mode: an amplitude-class
+  // one, or in bkgd_mode 0 of the 2-source layout sigma_x of the wide set)
+  if (r == bg_idx && lane == 2 * NSRC) mdl->bg = v;
 }
 
 // Per-walker cache (registers) of the current state's FAST3 column terms, for
@@ -1936,7 +2072,7 @@ __device__ __forceinline__ double sweep(const ModelDesc<NSRC> &m, const double2 
         // another sweep); the other set stays
         const int need = (hc->valid ? hc->stale : 3) | (hc->grp ? (hc->grp == 1 ? 2 : 1) : 0);
         if (need)
-          build_htab<NSRC, HS>(m, vtab, vtab, need, rows0, kc, (double)cw.S, lane, ExpTab{etab});
+          build_htab<NSRC, HS, true>(m, vtab, vtab, need, rows0, kc, (double)cw.S, lane, ExpTab{etab});
         hc->valid = 1;
         hc->stale = 0;
         hc->flip = hc->grp != 0;
