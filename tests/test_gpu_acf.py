@@ -10,7 +10,9 @@ its read-back) the comparison is np.array_equal.
 
 Shapes (W, N, ncols, L): a two-row series, fewer rows than a tile, N < L (lags >= N are
 exactly 0.0), more series than fit a slot, 24 and 20 columns (three and two column groups),
-several time tiles with a ragged last one, and both lag passes of L = 1024.
+several time tiles with a ragged last one, and both lag passes of L = 1024.  Those stay
+under 1024 units, one a workgroup; the shapes of tests/fold_scale_cases.py give a workgroup
+two or five.
 """
 import functools
 import json
@@ -20,6 +22,7 @@ import numpy as np
 import pytest
 
 import acf_restatement as ar
+import fold_scale_cases as fc
 from olpefit_amd import _lib, autocorr, step2, step3, synth
 from olpefit_amd.autocorr import Autocorr
 
@@ -139,6 +142,82 @@ def test_state_is_additive(lib_loaded):
         a.reset()
         st = a.state()
         assert (st["n"], st["series"], st["skipped"]) == (0, 0, 0) and not st["C"].any()
+
+
+# ---------------------------------------------------------------------------------------
+# Several units per workgroup (tests/fold_scale_cases.py; test_fold_plans_cpu.py asserts the
+# plans).  Above 1024 (series, time tile) units a workgroup of acf_fold_kernel walks a run of
+# them, re-staging its LDS per unit with the accumulators kept, and skips the units of an
+# unusable series ahead of its barrier.
+
+def knob(monkeypatch, tile):
+    if tile is None:
+        monkeypatch.delenv("OLPE_ACF_TILE", raising=False)
+    else:
+        monkeypatch.setenv("OLPE_ACF_TILE", tile)
+
+
+@pytest.mark.parametrize("time_major", [False, True])
+@pytest.mark.parametrize("name", list(fc.ACF))
+def test_several_units_per_workgroup(lib_loaded, monkeypatch, name, time_major):
+    """The shapes of fold_scale_cases.ACF: 2 or 5 units a workgroup, a last workgroup of one
+    unit, the two-pass kernel, workgroups whose units are of two series."""
+    W, N, ncols, L, tile = fc.ACF[name]
+    knob(monkeypatch, tile)
+    rows, ref = case(W, N, ncols, L)
+    data = np.ascontiguousarray(np.swapaxes(rows, 0, 1)) if time_major else rows
+    with Autocorr(ncols, L) as a:
+        a.fold_rows(data, time_major=time_major)
+        st = a.state()
+    assert (st["n"], st["series"], st["skipped"]) == (W * N, W, 0)
+    check(st, ref, W * N, f"{name} {(W, N, ncols, L)} tile {tile} time_major={time_major}")
+    if N <= L:
+        assert np.all(st["C"][:, N:] == 0.0)
+    assert np.all(st["C"][:, 0] > 0.0)
+
+
+def test_unused_units_inside_a_run(lib_loaded, monkeypatch):
+    """1100 series x 200 rows in tiles of 64: 4 units a series, 5 a workgroup.  Series 10, 11
+    and 21 hold a non-finite value: workgroup 8 (units 40 .. 44) has no used unit and must
+    leave zeros, not stale memory, in its partial sums; workgroup 9 begins with three unused
+    units and ends with two used ones; workgroup 16 ends with an unused unit.  Twice the same
+    bits; and the state equals the add of two half folds (other runs of units, so another
+    order of the same terms) within twice the bound."""
+    W, N, ncols, L, tile = fc.ACF_SKIP
+    knob(monkeypatch, tile)
+    rows, _ = case(W, N, ncols, L)
+    bad = rows.copy()
+    for k, s in enumerate(fc.ACF_BAD_SERIES):
+        bad[s, (0, N - 1, 77)[k], (3, 16, 9)[k]] = (np.nan, np.inf, -np.inf)[k]
+    ref = ar.lag_sums(bad, L)
+    assert (ref["skipped"], ref["series"], ref["n"]) == (3, W - 3, (W - 3) * N)
+    out = []
+    for tm in (False, False, True):
+        data = np.ascontiguousarray(np.swapaxes(bad, 0, 1)) if tm else bad
+        with Autocorr(ncols, L) as a:
+            # a fold of every series first, so that the partial sums of every workgroup hold
+            # numbers when the fold under test begins
+            a.fold_rows(rows)
+            a.reset()
+            a.fold_rows(data, time_major=tm)
+            st = a.state()
+        assert (st["n"], st["series"], st["skipped"]) == (ref["n"], ref["series"], ref["skipped"])
+        assert np.isfinite(st["C"]).all()
+        check(st, ref, ref["n"], f"unused units, time_major={tm}")
+        out.append(st)
+    assert np.array_equal(out[0]["C"], out[1]["C"])
+    with Autocorr(ncols, L) as a, Autocorr(ncols, L) as b:
+        a.fold_rows(bad[:W // 2])
+        b.fold_rows(bad[W // 2:])
+        a.add(b.state())
+        halves = a.state()
+    assert (halves["n"], halves["series"], halves["skipped"]) == \
+        (ref["n"], ref["series"], ref["skipped"])
+    check(halves, ref, ref["n"], "two half folds added")
+    dev = np.abs(out[0]["C"].astype(np.longdouble) - halves["C"].astype(np.longdouble))
+    r = float((dev / (4.0 * ref["n"] * U * ref["C"][:, :1])).max())
+    print(f"one fold against two half folds: max |dC| / bound = {r:.3e}")
+    assert r <= 2.0
 
 
 def test_sampler_device_chain(lib_loaded):

@@ -19,6 +19,7 @@ import os
 import numpy as np
 import pytest
 
+import fold_scale_cases as fc
 from astrom_restatement import RESTATE
 from olpefit_amd import _lib, fitsio, step2, step3, synth
 from olpefit_amd.astrometry import Astrometry, header_scalars, py2_str
@@ -150,6 +151,24 @@ def test_medians_are_exact_and_samples_match(lib_loaded, shape, variant):
         pa = samp[0][1]
         assert (pa < 0).any() and (pa > 0).any() and (pa == 0).any()
     check_parity(res, samp, restated(chain, s, variant, delta_r, with_tables=tab), n)
+
+
+@pytest.mark.parametrize("shape", list(fc.ASTROM))
+def test_medians_and_parity_past_the_grid_caps(lib_loaded, shape):
+    """Variant 2 with the tables at sample counts past the caps (tests/fold_scale_cases.py):
+    700 x 400 = 280,000 samples give the select's 1024 x 256 threads a second trip of their
+    grid-stride loops; 1025 x 1024 = 1,049,600 are past astrom_correct_kernel's 4096 x 256
+    threads and make 257 stage-1 partials for the 256 threads of astrom_reduce_stage2.  (The
+    NumPy restatement of the larger case takes 0.3 s with the tables, so they stay.)"""
+    W, rows, tab = fc.ASTROM[shape]
+    chain = make_chain(W, rows, 2, seed=31)
+    s = scalars(rotation_angle=10.0)
+    res, samp = device(chain, s, 2, 20.0, with_tables=tab)
+    for r, (sep, pa) in zip(res, samp):
+        assert sep.shape == (rows, W)
+        assert bits(r["sep_median"]) == bits(np.median(sep))
+        assert bits(r["pa_median"]) == bits(np.median(pa))
+    check_parity(res, samp, restated(chain, s, 2, 20.0, with_tables=tab), W * rows)
 
 
 # (rotation_angle, parantel) for a geometric PA of about 30 deg -> the branch it lands in

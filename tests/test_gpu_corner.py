@@ -14,6 +14,7 @@ import os
 import numpy as np
 import pytest
 
+import fold_scale_cases as fc
 from olpefit_amd import _lib, corner, fitsio, step2, step3, synth
 from olpefit_amd.corner import Corner
 
@@ -184,6 +185,37 @@ def test_counts_do_not_depend_on_the_split(lib_loaded):
         # empty folds are fine
         seven.fold_rows(rows[:0])
         assert seven.counts()["n"] == 100
+
+
+def test_two_upload_pieces(lib_loaded):
+    """fold_rows uploads pieces of 2^18 samples: 2^18 + 513 are two, the second one short
+    (513 samples: a block and one).  The counts are NumPy's and those of the two halves folded
+    one after the other."""
+    n, ncols, nb2, nb1 = fc.CORNER_PIECES
+    rows = posterior_rows((n,), ncols, 23)
+    rg = ranges_for(rows)
+    with Corner(rg, bins=nb2, fine_bins=nb1) as one, Corner(rg, bins=nb2, fine_bins=nb1) as two:
+        one.fold_rows(rows)
+        two.fold_rows(rows[:n // 2])
+        two.fold_rows(rows[n // 2:])
+        a, b = one.counts(), two.counts()
+        check_counts(a, rows, one.fine_edges, one.edges)
+    assert same(a, b) and a["outside1"].sum() > 0
+
+
+def test_more_chunks_than_the_grid_takes(lib_loaded):
+    """24 columns, 64 and 4,096 bins: 138 pair tiles, so launch_fold takes at most 2048 / 138
+    = 14 chunks of the samples; 57,345 samples (the smallest multiple of 512, plus one, with
+    more than 14 chunks of 4096) are cut into 13 chunks of 4,608, the last one short."""
+    n, ncols, nb2, nb1 = fc.CORNER_CHUNKS
+    want, cap, chunks = fc.corner_plan(n, fc.corner_tiles(ncols, nb2, nb1))
+    assert want > cap and chunks > 1
+    rows = posterior_rows((n,), ncols, 29)
+    with Corner(ranges_for(rows), bins=nb2, fine_bins=nb1) as c:
+        c.fold_rows(rows)
+        got = c.counts()
+        check_counts(got, rows, c.fine_edges, c.edges)
+    assert got["outside1"].sum() > 0 and got["h2"].sum() > 0
 
 
 def test_merge_equals_one_object(lib_loaded):

@@ -13,7 +13,8 @@ against its read-back) the comparison is np.array_equal.
 
 Shapes (W, N, ncols): one row; fewer rows than any tile; one under and one over 64 rows; one
 16-column block exactly; one and two columns; 24 columns with a ragged last tile; many walkers
-of few rows.
+of few rows.  Those stay under 2048 tiles, one a workgroup; the shapes of
+tests/fold_scale_cases.py give a workgroup two or three (the second half of this file).
 """
 import functools
 import json
@@ -24,6 +25,7 @@ import pytest
 
 import acf_restatement as ar
 import cov_restatement as cr
+import fold_scale_cases as fc
 from olpefit_amd import _lib, covariance as cv, fitsio, step2, step3, synth
 from olpefit_amd.covariance import Covariance
 
@@ -294,6 +296,156 @@ def test_sampler_device_chain(lib_loaded):
         assert t["n"] == W * 43 and t["nw"].tolist() == [43] * W      # ceil(300 / 7)
         assert np.array_equal(t["pivot"], chain2[0, 0])
         check(t, cr.sums(chain2[:, ::7]), "row_step 7")
+
+
+# ---------------------------------------------------------------------------------------
+# Several tiles per workgroup (tests/fold_scale_cases.py; test_fold_plans_cpu.py asserts
+# the plans).  Above 2048 tiles a workgroup of cov_fold_kernel walks a run of tiles: the next
+# tile's loads are in flight during a walk, the non-finite flags and the waves' column sums
+# alternate between two buffers, and a tile's sums are written one tile late.
+
+def between_check(bt, ref, W, label):
+    """test_sums_equal_the_restatement's bound on the between term, with every walker's own
+    row count (a walker may have lost rows) and m terms."""
+    nw = ref["nw"].astype(LD)
+    on = ref["nw"] > 0
+    d = np.sqrt(nw[:, None] * ref["S2w"])[on]                    # >= |S1w| by Cauchy-Schwarz
+    nmax, m = int(ref["nw"].max()), int(on.sum())
+    bound = (8 * nmax + 4 * m) * U * (d[:, :, None] * d[:, None, :] / nw[on][:, None, None]
+                                      ).sum(axis=0)
+    rb = worst(bt["B"] - ref["between"], bound)
+    print(f"{label} max |B - ref| / bound = {rb:.3e}")
+    assert rb <= 1.0 and np.array_equal(bt["B"], bt["B"].T), (label, rb)
+    assert (bt["m"], bt["nw_min"], bt["nw_max"]) == (ref["m"], ref["nw_min"], ref["nw_max"])
+
+
+@pytest.mark.parametrize("pooled", [False, True])
+@pytest.mark.parametrize("time_major", [False, True])
+@pytest.mark.parametrize("name", list(fc.COV))
+def test_several_tiles_per_workgroup(lib_loaded, monkeypatch, name, time_major, pooled):
+    """The shapes of fold_scale_cases.COV, each with more than 2048 tiles in the per-walker
+    form (2 or 3 a workgroup), in both layouts, per walker and pooled, under the bounds of
+    test_sums_equal_the_restatement.  Pooled, the rows are one walker's: only the 1100 x 257
+    case then still has more tiles than workgroups (4,418 of 64 rows, 3 a workgroup)."""
+    W, N, ncols, tile = fc.COV[name]
+    if tile is None:
+        monkeypatch.delenv("OLPE_COV_TILE", raising=False)
+    else:
+        monkeypatch.setenv("OLPE_COV_TILE", tile)
+    rows, ref = case(W, N, ncols)
+    label = f"{name} {(W, N, ncols)} tile {tile} time_major={time_major} pooled={pooled}"
+    with Covariance(ncols, walkers=0 if pooled else W) as c:
+        c.fold_rows(lay(rows, time_major), time_major=time_major)
+        st = c.state()
+        bt = None if pooled else c.between()
+    assert st["has_pivot"] and np.array_equal(st["pivot"], rows[0, 0])
+    assert st["walkers"] == (0 if pooled else W)
+    check(st, ref, label)
+    if not pooled:
+        between_check(bt, ref, W, label)
+
+
+@functools.lru_cache(maxsize=None)
+def pipeline_case():
+    """fold_scale_cases.COV_PIPE with non-finite rows where the tile pipeline turns (the
+    positions come from the plan), the explicit pivot and the restated sums."""
+    W, N, ncols, tile = fc.COV_PIPE
+    plan = fc.cov_plan(W, N, tile)
+    rows, _ = case(W, N, ncols)
+    bad = rows.copy()
+    spots, gone = fc.cov_bad_rows(plan, W, N)
+    for k, (w, r) in enumerate(spots):
+        bad[w, r, (5 * k + 3) % ncols] = (np.nan, np.inf, -np.inf, np.nan)[k]
+    bad[gone, :, 11] = np.nan
+    bad.setflags(write=False)
+    pivot = rows[0, 0].copy()
+    return bad, pivot, cr.sums(bad, pivot), plan, spots, gone
+
+
+def test_non_finite_rows_against_the_tile_pipeline(lib_loaded, monkeypatch):
+    """1100 walkers x 257 rows in tiles of 64: 3 tiles a workgroup.  A non-finite row in the
+    first tile of a run (its flag must be gone when the buffer is used again two tiles on), in
+    the second and the third tile of one run at the same row of the tile (one flag per
+    buffer), in a walker's last tile of one row, and a walker without a finite row (nw = 0:
+    the between term has W - 1 terms and nw_min is the others')."""
+    monkeypatch.setenv("OLPE_COV_TILE", "64")
+    bad, pivot, ref, plan, spots, gone = pipeline_case()
+    W, N, ncols, _ = fc.COV_PIPE
+    assert ref["skipped"] == len(spots) + N and ref["n"] == W * N - ref["skipped"]
+    assert ref["nw"][gone] == 0 and (ref["m"], ref["nw_min"], ref["nw_max"]) == (W - 1, N - 2, N)
+    for tm in (False, True):
+        with Covariance(ncols, walkers=W, pivot=pivot) as c:
+            c.fold_rows(lay(bad, tm), time_major=tm)
+            st, bt = c.state(), c.between()
+        assert np.array_equal(st["pivot"], pivot)
+        assert (st["n"], st["skipped"]) == (ref["n"], ref["skipped"])
+        for k in ("S1", "S2", "S1w"):
+            assert np.isfinite(st[k]).all(), k
+        assert not st["S1w"][gone].any() and st["nw"][gone] == 0
+        check(st, ref, f"pipeline non-finite, time_major={tm}")
+        between_check(bt, ref, W, f"pipeline non-finite, time_major={tm}")
+
+
+def test_walker_sums_do_not_depend_on_the_tiles_per_workgroup(lib_loaded, monkeypatch):
+    """A tile's column sums are the eight waves' in wave order, a walker's its tiles' in tile
+    order, whatever run of tiles a workgroup took: S1w and nw of the 3-tiles-a-workgroup fold
+    equal, bit for bit, those of the same rows folded 409 walkers at a time (2045 tiles, one a
+    workgroup: the path the small shapes pin), non-finite rows included.  The pooled sums add
+    in another order and stay under the bound; a repeated fold repeats every bit."""
+    monkeypatch.setenv("OLPE_COV_TILE", "64")
+    bad, pivot, ref, plan, _, _ = pipeline_case()
+    W, N, ncols, _ = fc.COV_PIPE
+    big = []
+    for _ in range(2):
+        with Covariance(ncols, walkers=W, pivot=pivot) as c:
+            c.fold_rows(bad)
+            big.append((c.state(), c.between()))
+    for k in ("S1", "S2", "S1w", "nw", "pivot"):
+        assert np.array_equal(big[0][0][k], big[1][0][k]), k
+    assert np.array_equal(big[0][1]["B"], big[1][1]["B"]) and big[0][0]["n"] == big[1][0]["n"]
+    per = fc.COV_MAX_SLOTS // plan["tpw"]
+    assert per == 409 and fc.cov_plan(per, N, "64")["chunk"] == 1
+    s1w, nw, n, skipped = [], [], 0, 0
+    S1, S2 = np.zeros(ncols, dtype=LD), np.zeros((ncols, ncols), dtype=LD)
+    for w0 in range(0, W, per):
+        part = bad[w0:w0 + per]
+        with Covariance(ncols, walkers=part.shape[0], pivot=pivot) as c:
+            c.fold_rows(part)
+            st = c.state()
+        s1w.append(st["S1w"])
+        nw.append(st["nw"])
+        n, skipped = n + st["n"], skipped + st["skipped"]
+        S1, S2 = S1 + st["S1"], S2 + st["S2"]
+    st = big[0][0]
+    assert np.array_equal(np.concatenate(s1w), st["S1w"])
+    assert np.array_equal(np.concatenate(nw), st["nw"])
+    assert (n, skipped) == (st["n"], st["skipped"]) == (ref["n"], ref["skipped"])
+    check(st, ref, "3 tiles a workgroup")
+    check({"S1": S1, "S2": S2, "n": n, "skipped": skipped, "walkers": 0}, ref,
+          "1 tile a workgroup, three objects")
+
+
+def test_sampler_device_chain_several_tiles(lib_loaded, monkeypatch):
+    """fold(sampler) of a device chain [1100][130][17] in tiles of 64: 3 tiles a walker, 3,300
+    tiles, 2 a workgroup, every third workgroup with tiles of two walkers.  The same bits as
+    fold_rows of the same rows, and under the bounds."""
+    from olpefit_amd.core import Sampler
+    monkeypatch.setenv("OLPE_COV_TILE", "64")
+    W, N, _ = fc.COV_CHAIN
+    img, _ = synth.make_image(32, 2, 0)
+    with Sampler(img, 1.0, 1, 1, 2, nsrc=2) as s:
+        assert s.ps == 17
+        rows, ref = case(W, N, s.ps)
+        s.seed(np.arange(1, W + 1))
+        s.test_chain_set(rows)
+        with Covariance(s.ps, W) as dev, Covariance(s.ps, W) as host:
+            dev.fold(s)
+            host.fold_rows(rows)
+            a, b = dev.state(), host.state()
+    for k in ("S1", "S2", "S1w", "nw", "pivot"):
+        assert np.array_equal(a[k], b[k]), k
+    assert (a["n"], a["skipped"]) == (b["n"], b["skipped"]) == (W * N, 0)
+    check(a, ref, "device chain, 2 tiles a workgroup")
 
 
 L4 = np.array([[1.0, 0.0, 0.0, 0.0], [0.8, 0.6, 0.0, 0.0], [-0.3, 0.2, 0.5, 0.0],

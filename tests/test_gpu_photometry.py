@@ -8,18 +8,22 @@ restatement in the operation order olpe_phot.hip states.
 * Order statistics: bit-equal to the sorted valid samples (the radix select is exact).  The
   select's and the reductions' workgroups hold 256 threads (kSelThreads of olpe_select.h,
   kThreads of olpe_phot.hip), so the sizes around a block are 255 / 256 / 257; a reduction
-  block covers 4096 samples (kChunk), so 4095 / 4096 / 4097 are here too.
+  block covers 4096 samples (kChunk), so 4095 / 4096 / 4097 are here too.  The select's grid
+  is 1024 such blocks and stage 2 of the reductions has 256 threads: 262,144, 262,145, 600,001
+  and 1,048,577 values (tests/fold_scale_cases.py) go past both.
 * Percentiles: ``np.nanpercentile`` to rtol 4e-16.  Mean and np.std: a np.longdouble
   restatement under the worst-case bound n * 2^-53 * max|x| of any summation order; the
   largest errors observed on this file's inputs were 4e-5 of that bound (mean) and 9e-4 (std).
 * fold(sampler) against fold_rows of the same launch: bit-identical.
 """
+import functools
 import json
 import os
 
 import numpy as np
 import pytest
 
+import fold_scale_cases as fc
 from olpefit_amd import _lib, fitsio, step2, step3, synth
 from olpefit_amd.astrometry import header_scalars, py2_str
 from olpefit_amd.photometry import (PLANES, Photometry, aperture_snr, reference_fwhm,
@@ -179,10 +183,16 @@ SELECT_CASES = select_cases()
 @pytest.mark.parametrize("case", list(SELECT_CASES))
 def test_order_statistics_and_moments(lib_loaded, case):
     values, W = SELECT_CASES[case]
+    check_order_statistics(values, W, case)
+
+
+def check_order_statistics(values, W, case):
+    """The checks of test_order_statistics_and_moments; returns every plane's summary."""
     chain = ratio_chain(values, W)
     with Photometry(W, chain.shape[0], pixscale=PIXSCALE) as p:
         p.fold_rows(chain)
-        res = p.finalize(PROBS)["flux_ratio"]
+        every = p.finalize(PROBS)
+        res = every["flux_ratio"]
         x = p.samples("flux_ratio").ravel()
     n = values.size
     assert np.array_equal(bits(x[:n]), bits(values)) and np.isnan(x[n:]).all()
@@ -211,6 +221,41 @@ def test_order_statistics_and_moments(lib_loaded, case):
         assert 0 < res["passes"] <= 1 + 5 * 5 + 5
     else:
         assert res["passes"] == 0                  # one value: nothing to select
+    return every
+
+
+@functools.lru_cache(maxsize=None)
+def scale_values(n):
+    """n values after the ties70k and signs recipes: half of them multiples of 1 / 7 (50
+    distinct values: ranks share bins down to the last digit), the rest a normal sample scaled
+    by 1, 1e-3 or 1e3, and +-0.0, +-5e-324, +-1e150: the keys differ from the first bit, so the
+    descent has all six digits to go."""
+    rng = np.random.RandomState(n % 100003)
+    special = [0.0, -0.0] * 4 + [5e-324, -5e-324, 1e150, -1e150]
+    m = n - n // 2 - len(special)
+    v = np.concatenate([rng.randint(-20, 30, size=n // 2) / 7.0,
+                        rng.normal(size=m) * rng.choice([1.0, 1e-3, 1e3], size=m), special])
+    rng.shuffle(v)
+    assert v.size == n
+    v.setflags(write=False)
+    return v
+
+
+@pytest.mark.parametrize("case", list(fc.PHOT))
+def test_order_statistics_past_the_grid_caps(lib_loaded, case):
+    """Sample counts past the caps (tests/fold_scale_cases.py): the select's 1024 x 256 threads
+    make no second trip of their grid-stride loops at 262,144 samples, one (one block) at
+    262,145 + padding, a third for part of the grid at 600,001; 1,048,577 values in rows of
+    1024 walkers are 257 stage-1 partials for the 256 threads of phot_reduce_stage2.  The
+    checks are test_order_statistics_and_moments'.  With +-1e150 among the values the bound on
+    the mean says little; the core_fraction plane of the same rows is 0.5 in every usable
+    sample, whose sums are exact in any order: n, mean 0.5 and std 0 exactly, which a dropped
+    or doubled partial would miss."""
+    n, W = fc.PHOT[case]
+    every = check_order_statistics(scale_values(n), W, case)
+    core = every["core_fraction"]
+    assert (core["n"], core["mean"], core["std"]) == (n, 0.5, 0.0)
+    assert core["min"] == core["max"] == 0.5 and core["passes"] == 0
 
 
 def test_a_plane_without_numbers(lib_loaded):
