@@ -187,6 +187,24 @@ __device__ __forceinline__ void st_coef(double *s, const Coef &k) {
   s[0] = k.a; s[1] = k.b; s[2] = k.c;
 }
 
+// ++*p on an LDS word by the calling lane(s): one ds_add_u32, or ds_add_rtn_u32 where the
+// old value is wanted.  Written as the instruction: the compiler expands an atomic add
+// into a count of the active lanes (two v_mbcnt, a compare, a branch) although one lane
+// calls it, which cost more VALU instructions than the read-modify-write it replaces.
+// A wave's LDS operations complete in order, so the compiler's own lgkmcnt waits stay
+// sufficient with this one in the queue.
+__device__ __forceinline__ void lds_inc(uint32_t *p) {
+  const unsigned a = (unsigned)(size_t)(__attribute__((address_space(3))) uint32_t *)p;
+  asm volatile("ds_add_u32 %0, %1" : : "v"(a), "v"(1u) : "memory");
+}
+__device__ __forceinline__ uint32_t lds_inc_rtn(uint32_t *p) {
+  const unsigned a = (unsigned)(size_t)(__attribute__((address_space(3))) uint32_t *)p;
+  uint32_t old;
+  asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)"
+               : "=v"(old) : "v"(a), "v"(1u) : "memory");
+  return old;
+}
+
 // Work-unit hand-off between waves of one launch (possibly on different XCDs), the
 // publish/consume protocol of cdna_hip_programming.md Guideline 16 (R1): the producing
 // wave stores the walker's words write-through (sc1: state, counters, RNG position and
@@ -504,11 +522,27 @@ void olpe_gibbs_kernel(GibbsArgs A) {
       mt.template draw<NP>(lane, 0, 2, r0, g, dice_idx);
       const int r = __builtin_amdgcn_readfirstlane(r0);
       // total_tries[rand] += 1  (:304)
-      const uint32_t tr = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_tries[r]) + 1u;
-      wave_sync();
-      if (lane == 0) s_tries[r] = tr;
-      if (A.accept_min > 0 && tr == (uint32_t)A.accept_min) {
-        if (++ndone == NP && done_at < 0) done_at = A.count0 + it + 1;
+      if constexpr (FAST) {
+        // one LDS add by lane 0 (the wave's LDS operations run in order, so the counter
+        // needs no wave_sync of its own); the sum comes back only where accept_min needs it
+        if (A.accept_min > 0) {
+          uint32_t old = 0;
+          if (lane == 0) old = lds_inc_rtn(s_tries + r);
+          const uint32_t tr = (uint32_t)__builtin_amdgcn_readfirstlane((int)old) + 1u;
+          if (tr == (uint32_t)A.accept_min) {
+            if (++ndone == NP && done_at < 0) done_at = A.count0 + it + 1;
+          }
+        } else {
+          if (lane == 0) lds_inc(s_tries + r);
+        }
+      } else {
+        // (EXACT: the read-modify-write as it was, so that those samplers' code is unchanged)
+        const uint32_t tr = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_tries[r]) + 1u;
+        wave_sync();
+        if (lane == 0) s_tries[r] = tr;
+        if (A.accept_min > 0 && tr == (uint32_t)A.accept_min) {
+          if (++ndone == NP && done_at < 0) done_at = A.count0 + it + 1;
+        }
       }
 
       // proposal / logproposal (:63-70, :306-309): loc + scale*gauss
@@ -644,7 +678,9 @@ void olpe_gibbs_kernel(GibbsArgs A) {
       // rejects in both)
       const double dchi = chi - st[PS - 1];
       const double la = -dchi / 2.;
-      const double dice = drawtab[dice_idx];
+      // (FAST tests the threshold: its dice is read only for the trace row, below)
+      double dice = 0.0;
+      if constexpr (!FAST) dice = drawtab[dice_idx];
       bool acc;
       uint32_t acc_bit;
       if constexpr (FAST) {
@@ -680,7 +716,8 @@ void olpe_gibbs_kernel(GibbsArgs A) {
       }
       wave_sync();
       if (acc && lane == 0) {
-        s_acc[r] = s_acc[r] + 1u;
+        if constexpr (FAST) lds_inc(s_acc + r);
+        else s_acc[r] = s_acc[r] + 1u;
         st[r] = nv;
         if (grp) {
           double *dt = st + (grp == 1 ? WS::OT1 : WS::OT2);
@@ -697,7 +734,7 @@ void olpe_gibbs_kernel(GibbsArgs A) {
         t[0] = (double)r;
         t[1] = nv;
         t[2] = chi_u;
-        t[3] = dice;
+        t[3] = FAST ? drawtab[dice_idx] : dice;
         t[4] = FAST ? (la_u == la_u ? ExpTab{etab}(la_u) : la_u) : exp(la_u);   // p_accept
         t[5] = acc ? 1.0 : 0.0;
        }
