@@ -42,6 +42,7 @@
 #include "../../include/olpe.h"
 #include "olpe_fold.h"
 #include "olpe_internal.h"
+#include "olpe_reduce.h"
 
 using namespace olpe;
 
@@ -292,22 +293,14 @@ __global__ __launch_bounds__(256) void acf_reduce0_kernel(
     sum += c0[(size_t)s * C + c];
     nu += (unsigned long long)use[s];
   }
-  red[threadIdx.x] = sum;
-  used[threadIdx.x] = nu;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) {
-      red[threadIdx.x] += red[threadIdx.x + h];
-      used[threadIdx.x] += used[threadIdx.x + h];
-    }
-    __syncthreads();
-  }
+  sum = block_sum<256>(sum, red);
+  nu = block_word<256, WordSum>(nu, used);
   if (threadIdx.x == 0) {
-    Cout[(size_t)c * (L + 1) + L] += red[0];
+    Cout[(size_t)c * (L + 1) + L] += sum;
     if (c == 0) {
-      cnt[0] += used[0] * (unsigned long long)N;
-      cnt[1] += used[0];
-      cnt[2] += (unsigned long long)nser - used[0];
+      cnt[0] += nu * (unsigned long long)N;
+      cnt[1] += nu;
+      cnt[2] += (unsigned long long)nser - nu;
     }
   }
 }
@@ -482,12 +475,10 @@ int olpe_acf_fold_ctx(olpe_acf *h, olpe_ctx *c) {
   HIPCHK(hipSetDevice(h->device));
   const long long N = c->chain_rows;
   if (N > 0 && (rc = reserve(h, c->W))) return rc;
-  fold_mark(h, c);
-  if (N == 0 || c->W == 0) return OLPE_OK;
-  if ((rc = fold_enter(h, c))) return rc;
   // [W][nrec][PS]: a walker's rows of this launch are one series
-  if ((rc = launch_fold(h, c->stream, c->d_chain, N * c->ps, c->ps, c->W, N))) return rc;
-  return fold_leave(h, c);
+  return fold_run(h, c, N > 0 && c->W > 0, [&](hipStream_t s) {
+    return launch_fold(h, s, c->d_chain, N * c->ps, c->ps, c->W, N);
+  });
 }
 
 int olpe_acf_fold_rows(olpe_acf *h, const double *rows, long long nwalkers, long long nrows,

@@ -27,33 +27,25 @@
 #include <vector>
 
 #include "../../include/olpe.h"
-#include "olpe_fold.h"
 #include "olpe_internal.h"
+#include "olpe_reduce.h"
 #include "olpe_select.h"
+#include "olpe_store.h"
 
 using namespace olpe;
 
-struct olpe_astrom : FoldBase {
-  int variant = 2;
-  int ps = 17;
+// the store holds [npairs][2] planes: sep and pa per pair
+struct olpe_astrom : SampleStore {
   int npairs = 1;
   int cols[2][4] = {};        // per pair: x / y of the primary, x / y of the companion
   bool have_tab = false;
   int tny = 0, tnx = 0, xdiff = 0, ydiff = 0;
   double pixscale = 0, rotation_angle = 0, rotcorr = 0;
   int use_rotcorr = 0;
-  long long W = 0, cap = 0;   // walkers, row capacity per walker
-  long long rows = 0;         // rows folded per walker
   bool finalized = false;
   double *d_xd = nullptr, *d_yd = nullptr;
-  double *d_store = nullptr;  // [npairs][2][cap * W]
   double *d_pos = nullptr;    // [cap * G][npairs][4] block sums of the positions
-  double *d_part = nullptr;   // [4][nblk] reduction partials
-  double *d_out = nullptr;    // [8] reduction results
-  unsigned long long *d_words = nullptr;  // [0] bad rows, [1..4] min / max keys of sep and pa, [5] next key
-  unsigned long long *d_hist = nullptr;   // [kSelBins]
-  double *d_stage = nullptr;  // upload staging of fold_rows
-  size_t stage_cap = 0;
+  // d_part [4][nblk], d_out [8], d_words [1..4] min / max keys of sep and pa, [5] next key
 };
 
 namespace {
@@ -71,19 +63,6 @@ struct FoldCfg {
   int use_rotcorr;
   const double *xd, *yd;
 };
-
-// fixed-order tree over the block (every thread takes part)
-__device__ double block_sum(double v, double *red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = kThreads / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
 
 // x + 1 (:211-214), np.int_ (:234-237), + diff (:244-247); false if the position cannot
 // index the table (non-finite, or an index outside it): nothing is loaded then
@@ -149,7 +128,7 @@ __global__ __launch_bounds__(kThreads) void astrom_fold_kernel(
       store[(size_t)(2 * p + 1) * N + at] = pa;
     }
     for (int k = 0; k < 4; ++k) {
-      const double s = block_sum(v[k], red);
+      const double s = block_sum<kThreads>(v[k], red);
       if (threadIdx.x == 0) pos[pblk + p * 4 + k] = s;
     }
   }
@@ -171,7 +150,7 @@ struct CorrCfg {
 __global__ __launch_bounds__(kThreads) void astrom_correct_kernel(
     double *__restrict__ sepv, double *__restrict__ pav, long long n, CorrCfg c,
     unsigned long long *__restrict__ words) {
-  __shared__ unsigned long long lo[2][kThreads], hi[2][kThreads];
+  __shared__ unsigned long long red[kThreads];
   unsigned long long mn[2] = {~0ull, ~0ull}, mx[2] = {0ull, 0ull};
   for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n;
        i += (long long)gridDim.x * kThreads) {
@@ -195,25 +174,14 @@ __global__ __launch_bounds__(kThreads) void astrom_correct_kernel(
     mx[1] = k1 > mx[1] ? k1 : mx[1];
   }
   for (int q = 0; q < 2; ++q) {
-    lo[q][threadIdx.x] = mn[q];
-    hi[q][threadIdx.x] = mx[q];
-  }
-  __syncthreads();
-  for (int o = kThreads / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) {
-      for (int q = 0; q < 2; ++q) {
-        const unsigned long long l = lo[q][threadIdx.x + o], h = hi[q][threadIdx.x + o];
-        if (l < lo[q][threadIdx.x]) lo[q][threadIdx.x] = l;
-        if (h > hi[q][threadIdx.x]) hi[q][threadIdx.x] = h;
-      }
-    }
-    __syncthreads();
+    mn[q] = block_word<kThreads, WordMin>(mn[q], red);
+    mx[q] = block_word<kThreads, WordMax>(mx[q], red);
   }
   if (threadIdx.x == 0) {      // integer min / max: the same whatever the order
-    atomicMin(&words[0], lo[0][0]);
-    atomicMax(&words[1], hi[0][0]);
-    atomicMin(&words[2], lo[1][0]);
-    atomicMax(&words[3], hi[1][0]);
+    atomicMin(&words[0], mn[0]);
+    atomicMax(&words[1], mx[0]);
+    atomicMin(&words[2], mn[1]);
+    atomicMax(&words[3], mx[1]);
   }
 }
 
@@ -270,57 +238,40 @@ __global__ __launch_bounds__(kThreads) void astrom_reduce_stage1(
     }
   }
   for (int k = 0; k < nv; ++k) {
-    const double t = block_sum(s[k], red);
+    const double t = block_sum<kThreads>(s[k], red);
     if (threadIdx.x == 0) part[(size_t)k * nblk + blockIdx.x] = t;
   }
 }
 
-// stage 2: one block per value, the blocks' partials in a fixed order
-__global__ __launch_bounds__(kThreads) void astrom_reduce_stage2(const double *__restrict__ part,
-                                                                 int nblk,
-                                                                 double *__restrict__ out) {
-  __shared__ double red[kThreads];
-  const double *p = part + (size_t)blockIdx.x * nblk;
-  double a = 0.0;
-  for (int b = threadIdx.x; b < nblk; b += kThreads) a += p[b];
-  a = block_sum(a, red);
-  if (threadIdx.x == 0) out[blockIdx.x] = a;
-}
-
-// sums of `nv` values over n samples into host out[nv]
+// sums of `nv` values over n samples into host out[nv]: stage 2 is one block per value, the
+// blocks' partials in a fixed order
 int reduce(olpe_astrom *a, const double *x, const double *y, long long n, const RedCfg &c,
            int nv, double *out) {
   const int nblk = (int)((n + kChunk - 1) / kChunk);
   hipLaunchKernelGGL(astrom_reduce_stage1, dim3(nblk), dim3(kThreads), 0, a->stream, x, y, n, c,
                      nblk, a->d_part);
   HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(astrom_reduce_stage2, dim3(nv), dim3(kThreads), 0, a->stream, a->d_part,
-                     nblk, a->d_out);
+  hipLaunchKernelGGL(reduce_stage2_kernel<kThreads>, dim3(nv), dim3(kThreads), 0, a->stream,
+                     a->d_part, nblk, a->d_out);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out, a->d_out, nv * sizeof(double), hipMemcpyDeviceToHost, a->stream));
   HIPCHK(hipStreamSynchronize(a->stream));
   return OLPE_OK;
 }
 
-// np.median of x[0..n): the order statistic (n - 1) / 2 by radix select below the common
-// prefix of the keys (kmin / kmax: their extremes), the one after it where n is even, and
-// their mean (olpe_select.h)
+// np.median of x[0..n): the bracket at the virtual index (n - 1) / 2 (exact in a double: n <=
+// 2^40) by radix select below the common prefix of the keys (kmin / kmax: their extremes),
+// and where n is even the mean of the pair (olpe_select.h)
 int median(olpe_astrom *a, const double *x, long long n, unsigned long long kmin,
            unsigned long long kmax, double *out) {
-  const long long k1 = (n - 1) / 2, k2 = n / 2;
-  SelRank r;
-  r.k = k1;
+  const double mid = (double)(n - 1) * 0.5;
+  unsigned long long k1, k2;
   int rc;
-  if ((rc = select_ranks(a->stream, a->d_hist, x, n, (unsigned long long)n, kmin, kmax, &r, 1,
-                         nullptr)))
+  if ((rc = select_brackets(a->stream, a->d_hist, a->d_words + 5, x, n, (unsigned long long)n,
+                            kmin, kmax, &mid, 1, &k1, &k2, nullptr)))
     return rc;
-  unsigned long long key2 = r.key;
-  // keys <= r.key: those below it and its copies
-  if ((unsigned long long)k2 >= r.below + r.equal &&
-      (rc = select_next(a->stream, a->d_words + 5, x, n, r.key, kmax, &key2, nullptr)))
-    return rc;
-  const double v1 = okey_inv(r.key), v2 = okey_inv(key2);
-  *out = k1 == k2 ? v1 : (v1 + v2) / 2.0;                  // np.mean of the middle pair
+  const double v1 = okey_inv(k1), v2 = okey_inv(k2);
+  *out = n % 2 ? v1 : (v1 + v2) / 2.0;                     // np.mean of the middle pair
   return OLPE_OK;
 }
 
@@ -379,10 +330,8 @@ int olpe_astrom_create(int device, int variant, int ps, const int *pair_cols, in
     return set_err(OLPE_EINVAL, "distortion tables of %d x %d", tab_ny, tab_nx);
   if (!isfinite(pixscale) || !isfinite(rotation_angle) || (use_rotcorr && !isfinite(rotcorr)))
     return set_err(OLPE_EINVAL, "non-finite pixscale / rotation_angle / rotcorr");
-  if (walkers < 1 || row_cap < 1 || walkers > (65535ll * kThreads) || row_cap > 0x7fffffffll ||
-      walkers > (1ll << 40) / row_cap)
-    return set_err(OLPE_EINVAL, "walkers %lld x row capacity %lld", walkers, row_cap);
   int rc;
+  if ((rc = store_geometry(walkers, row_cap, kThreads))) return rc;
   if ((rc = open_device(device))) return rc;
   olpe_astrom *a = new olpe_astrom;
   a->variant = variant;
@@ -446,16 +395,12 @@ int olpe_astrom_fold_ctx(olpe_astrom *a, olpe_ctx *c) {
   int rc;
   if ((rc = fold_check(a, c))) return rc;
   const long long nrec = c->chain_rows;
-  if (a->rows + nrec > a->cap)
-    return set_err(OLPE_ESTATE, "sample store full: %lld + %lld rows per walker, capacity %lld",
-                   a->rows, nrec, a->cap);
+  if ((rc = store_room(a, nrec))) return rc;
   HIPCHK(hipSetDevice(a->device));
-  fold_mark(a, c);
-  if (nrec == 0) return OLPE_OK;
-  if ((rc = fold_enter(a, c))) return rc;
-  if ((rc = launch_fold(a, c->stream, c->d_chain, nrec * c->ps, c->ps, fold_cfg(a), nrec)))
+  if ((rc = fold_run(a, c, nrec > 0, [&](hipStream_t s) {
+         return launch_fold(a, s, c->d_chain, nrec * c->ps, c->ps, fold_cfg(a), nrec);
+       })))
     return rc;
-  if ((rc = fold_leave(a, c))) return rc;
   a->rows += nrec;
   return OLPE_OK;
 }
@@ -463,13 +408,9 @@ int olpe_astrom_fold_ctx(olpe_astrom *a, olpe_ctx *c) {
 int olpe_astrom_fold_rows(olpe_astrom *a, const double *rows, long long nrows) {
   if (!a || nrows < 0 || (nrows > 0 && !rows)) return set_err(OLPE_EINVAL, "bad argument");
   if (a->finalized) return set_err(OLPE_ESTATE, "fold after finalize");
-  if (a->rows + nrows > a->cap)
-    return set_err(OLPE_ESTATE, "sample store full: %lld + %lld rows per walker, capacity %lld",
-                   a->rows, nrows, a->cap);
-  if (nrows == 0) return OLPE_OK;
-  HIPCHK(hipSetDevice(a->device));
   int rc;
-  if ((rc = wait_pending(a))) return rc;
+  if ((rc = store_room(a, nrows))) return rc;
+  if (nrows == 0) return OLPE_OK;
   // only the position columns travel: [rows][W][nu], the pairs' columns renumbered
   int uniq[8], nu = 0;
   FoldCfg f = fold_cfg(a);
@@ -481,23 +422,17 @@ int olpe_astrom_fold_rows(olpe_astrom *a, const double *rows, long long nrows) {
       f.cols[p][k] = j;
     }
   const long long per_row = a->W * nu;
-  const long long chunk = std::max(1ll, std::min(nrows, (long long)(1 << 23) / per_row));
-  if ((rc = grow((void **)&a->d_stage, &a->stage_cap, (size_t)(chunk * per_row) * 8,
-                 "the row upload")))
-    return rc;
-  std::vector<double> pack((size_t)(chunk * per_row));
-  for (long long r0 = 0; r0 < nrows; r0 += chunk) {
-    const long long nr = std::min(chunk, nrows - r0);
-    const double *src = rows + (size_t)r0 * a->W * a->ps;
-    for (long long i = 0; i < nr * a->W; ++i)
-      for (int j = 0; j < nu; ++j) pack[(size_t)i * nu + j] = src[(size_t)i * a->ps + uniq[j]];
-    HIPCHK(hipMemcpyAsync(a->d_stage, pack.data(), (size_t)(nr * per_row) * 8,
-                          hipMemcpyHostToDevice, a->stream));
-    if ((rc = launch_fold(a, a->stream, a->d_stage, nu, per_row, f, nr))) return rc;
-    HIPCHK(hipStreamSynchronize(a->stream));   // pack / d_stage are reused
-    a->rows += nr;
-  }
-  return OLPE_OK;
+  std::vector<double> pack;
+  return store_upload(
+      a, nrows, per_row,
+      [&](long long r0, long long nr) {
+        const double *src = rows + (size_t)r0 * a->W * a->ps;
+        pack.resize((size_t)(nr * per_row));     // the first piece is the largest
+        for (long long i = 0; i < nr * a->W; ++i)
+          for (int j = 0; j < nu; ++j) pack[(size_t)i * nu + j] = src[(size_t)i * a->ps + uniq[j]];
+        return pack.data();
+      },
+      [&](long long nr) { return launch_fold(a, a->stream, a->d_stage, nu, per_row, f, nr); });
 }
 
 int olpe_astrom_finalize(olpe_astrom *a, double delta_r, double parantel, double *out) {
@@ -517,12 +452,11 @@ int olpe_astrom_finalize(olpe_astrom *a, double delta_r, double parantel, double
     return set_err(OLPE_EINVAL, "%llu sample(s) with a non-finite position or a distortion-table "
                    "index outside the table", bad);
   const long long n = a->rows * a->W;
-  const size_t N = (size_t)a->W * a->cap;
   const double fn = (double)n;
   const long long nposblk = a->rows * groups(a);
   for (int p = 0; p < a->npairs; ++p) {
     double *o = out + (size_t)p * OLPE_ASTROM_LEN;
-    double *sep = a->d_store + (size_t)(2 * p) * N, *pa = a->d_store + (size_t)(2 * p + 1) * N;
+    double *sep = store_plane(a, 2 * p), *pa = store_plane(a, 2 * p + 1);
     RedCfg r = {};
     r.variant = a->variant;
     // means of the de-distorted positions (reported; they feed nothing else)
@@ -610,23 +544,17 @@ int olpe_astrom_finalize(olpe_astrom *a, double delta_r, double parantel, double
   return OLPE_OK;
 }
 
-int olpe_astrom_rows(olpe_astrom *a, long long *rows) {
-  if (!a || !rows) return set_err(OLPE_EINVAL, "NULL argument");
-  *rows = a->rows;
-  return OLPE_OK;
-}
+int olpe_astrom_rows(olpe_astrom *a, long long *rows) { return store_rows(a, rows); }
 
 int olpe_astrom_samples(olpe_astrom *a, int pair, double *out) {
   if (!a || !out) return set_err(OLPE_EINVAL, "NULL argument");
   if (pair < 0 || pair >= a->npairs) return set_err(OLPE_EINVAL, "pair %d of %d", pair, a->npairs);
   if (!a->finalized) return set_err(OLPE_ESTATE, "samples before finalize");
   HIPCHK(hipSetDevice(a->device));
-  const size_t n = (size_t)a->rows * a->W, N = (size_t)a->W * a->cap;
   HIPCHK(hipStreamSynchronize(a->stream));
-  HIPCHK(hipMemcpy(out, a->d_store + (size_t)(2 * pair) * N, n * 8, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(out + n, a->d_store + (size_t)(2 * pair + 1) * N, n * 8,
-                   hipMemcpyDeviceToHost));
-  return OLPE_OK;
+  int rc;
+  if ((rc = store_read(a, 2 * pair, out))) return rc;
+  return store_read(a, 2 * pair + 1, out + (size_t)a->rows * a->W);
 }
 
 }  // extern "C"

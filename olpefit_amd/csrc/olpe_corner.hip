@@ -387,11 +387,10 @@ int olpe_corner_fold_ctx(olpe_corner *h, olpe_ctx *c) {
   if ((rc = fold_check(h, c))) return rc;
   const long long n = (long long)c->W * c->chain_rows;
   HIPCHK(hipSetDevice(h->device));
-  fold_mark(h, c);
-  if (n == 0) return OLPE_OK;
-  if ((rc = fold_enter(h, c))) return rc;
-  if ((rc = launch_fold(h, c->stream, c->d_chain, n))) return rc;   // [W][nrec][PS]: n rows
-  if ((rc = fold_leave(h, c))) return rc;
+  if ((rc = fold_run(h, c, n > 0, [&](hipStream_t s) {
+         return launch_fold(h, s, c->d_chain, n);               // [W][nrec][PS]: n rows
+       })))
+    return rc;
   h->n += (unsigned long long)n;
   return OLPE_OK;
 }

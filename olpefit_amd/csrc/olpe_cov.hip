@@ -45,6 +45,7 @@
 #include "../../include/olpe.h"
 #include "olpe_fold.h"
 #include "olpe_internal.h"
+#include "olpe_reduce.h"
 
 using namespace olpe;
 
@@ -269,17 +270,6 @@ cov_fold_kernel(const FoldArgs a) {
   }
 }
 
-// fixed tree over the workgroup's kRedThreads values
-__device__ double tree_sum(double v, double *red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = kRedThreads / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 // A workgroup per output: S2[j][k] for j <= k (blocks 0 .. C C - 1; j > k has nothing to
 // do), S1[c] (C C .. C C + C - 1), the counters (the last).  Thread i adds the partial sums
 // of workgroups i, i + 256, ..., then the fixed tree.
@@ -302,7 +292,7 @@ __global__ __launch_bounds__(kRedThreads) void cov_reduce_kernel(
     }
     double s = 0.0;
     for (int b = threadIdx.x; b < slots; b += kRedThreads) s += part[(size_t)b * stride + at];
-    const double tot = tree_sum(s, red);
+    const double tot = block_sum<kRedThreads>(s, red);
     if (threadIdx.x == 0) {
       if (o < C * C) {
         const double nv = S2[j * C + k] + tot;
@@ -316,15 +306,10 @@ __global__ __launch_bounds__(kRedThreads) void cov_reduce_kernel(
   }
   unsigned long long n = 0;
   for (int b = threadIdx.x; b < slots; b += kRedThreads) n += partn[b];
-  redn[threadIdx.x] = n;
-  __syncthreads();
-  for (int h = kRedThreads / 2; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) redn[threadIdx.x] += redn[threadIdx.x + h];
-    __syncthreads();
-  }
+  n = block_word<kRedThreads, WordSum>(n, redn);
   if (threadIdx.x == 0) {
-    cnt[0] += redn[0];
-    cnt[1] += rows - redn[0];
+    cnt[0] += n;
+    cnt[1] += rows - n;
   }
 }
 
@@ -355,7 +340,7 @@ __global__ __launch_bounds__(kRedThreads) void cov_between_kernel(
     const double *__restrict__ S1w, const unsigned long long *__restrict__ nw, long long W, int C,
     double *__restrict__ out) {
   __shared__ double red[kRedThreads];
-  __shared__ unsigned long long rw[3][kRedThreads];
+  __shared__ unsigned long long rw[kRedThreads];
   const int j = blockIdx.x / C, k = blockIdx.x - j * C;
   if (j > k) return;
   double s = 0.0;
@@ -368,30 +353,20 @@ __global__ __launch_bounds__(kRedThreads) void cov_between_kernel(
     lo = n < lo ? n : lo;
     hi = n > hi ? n : hi;
   }
-  const double tot = tree_sum(s, red);
+  const double tot = block_sum<kRedThreads>(s, red);
   if (threadIdx.x == 0) {
     out[j * C + k] = tot;
     out[k * C + j] = tot;
   }
   if (blockIdx.x) return;
-  rw[0][threadIdx.x] = m;
-  rw[1][threadIdx.x] = lo;
-  rw[2][threadIdx.x] = hi;
-  __syncthreads();
-  for (int h = kRedThreads / 2; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) {
-      rw[0][threadIdx.x] += rw[0][threadIdx.x + h];
-      const unsigned long long l2 = rw[1][threadIdx.x + h], h2 = rw[2][threadIdx.x + h];
-      if (l2 < rw[1][threadIdx.x]) rw[1][threadIdx.x] = l2;
-      if (h2 > rw[2][threadIdx.x]) rw[2][threadIdx.x] = h2;
-    }
-    __syncthreads();
-  }
+  m = block_word<kRedThreads, WordSum>(m, rw);
+  lo = block_word<kRedThreads, WordMin>(lo, rw);
+  hi = block_word<kRedThreads, WordMax>(hi, rw);
   if (threadIdx.x == 0) {
     unsigned long long *ow = reinterpret_cast<unsigned long long *>(out + (size_t)C * C);
-    ow[0] = rw[0][0];
-    ow[1] = rw[0][0] ? rw[1][0] : 0;
-    ow[2] = rw[2][0];
+    ow[0] = m;
+    ow[1] = m ? lo : 0;
+    ow[2] = hi;
   }
 }
 
@@ -566,13 +541,10 @@ int olpe_cov_fold_ctx(olpe_cov *h, olpe_ctx *c, int row_step) {
   // rows 0, row_step, ... of the chain [W][nrec][PS]: indexing only
   const long long N = (c->chain_rows + row_step - 1) / row_step;
   if (N > 0 && c->W > 0 && (rc = reserve(h, tiles_of(h, c->W, N)))) return rc;
-  fold_mark(h, c);
-  if (N == 0 || c->W == 0) return OLPE_OK;
-  if ((rc = fold_enter(h, c))) return rc;
-  if ((rc = launch_fold(h, c->stream, c->d_chain, c->chain_rows * c->ps,
-                        (long long)row_step * c->ps, c->W, N, 0)))
-    return rc;
-  return fold_leave(h, c);
+  return fold_run(h, c, N > 0 && c->W > 0, [&](hipStream_t s) {
+    return launch_fold(h, s, c->d_chain, c->chain_rows * c->ps, (long long)row_step * c->ps,
+                       c->W, N, 0);
+  });
 }
 
 int olpe_cov_fold_rows(olpe_cov *h, const double *rows, long long nwalkers, long long nrows,

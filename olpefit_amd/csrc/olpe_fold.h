@@ -1,6 +1,7 @@
 // olpe_fold.h -- what the step-3 fold objects (olpe_astrom, olpe_corner, olpe_resid,
-// olpe_acf) share on the host: the device, a stream and an event of their own, device
-// buffers, and the one statement of how a fold joins a sampler's stream.  No device code.
+// olpe_acf, olpe_phot, olpe_cov) share on the host: the device, a stream and an event of
+// their own, device buffers, and the one statement of how a fold joins a sampler's stream
+// (fold_run).  No device code.
 //
 // A fold object belongs to a device, not to a sampler context.  It folds a context's last
 // launch at most once, asynchronously on that context's stream: the fold runs behind the
@@ -98,10 +99,9 @@ inline int drain(FoldBase *b) {
   return OLPE_OK;
 }
 
-// A fold of context c's last launch, in the caller's order:
-//   fold_check   there is a launch, and this object has not folded it
-//   fold_mark    it counts as folded from here on, rows or none
-//   fold_enter / the caller's launches on c->stream / fold_leave
+// A fold of context c's last launch: the caller checks its arguments and fold_check (there
+// is a launch, and this object has not folded it), refuses what does not fit, sets the
+// device and reserves what the launches need; fold_run does the rest.
 inline int fold_check(const FoldBase *b, const olpe_ctx *c) {
   if (!c->d_state || !c->launches) return set_err(OLPE_ESTATE, "no sampler launch yet");
   if (b->last_ctx == c && b->last_launch == c->launches)
@@ -129,6 +129,19 @@ inline int fold_leave(FoldBase *b, const olpe_ctx *c) {
   HIPCHK(hipEventRecord(b->ev, c->stream));
   b->ev_pending = true;
   return OLPE_OK;
+}
+
+// The fold's place on the sampler's stream: the launch counts as folded from here on, rows
+// or none (fold_mark); with anything to do (`any`), launch(c->stream) runs between
+// fold_enter and fold_leave.  The caller bumps its counters when this returns OLPE_OK.
+template <class Launch>
+int fold_run(FoldBase *b, const olpe_ctx *c, bool any, Launch launch) {
+  fold_mark(b, c);
+  if (!any) return OLPE_OK;
+  int rc;
+  if ((rc = fold_enter(b, c))) return rc;
+  if ((rc = launch(c->stream))) return rc;
+  return fold_leave(b, c);
 }
 
 // reset: the launch folded last may be folded again

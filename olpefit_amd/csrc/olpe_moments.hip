@@ -28,7 +28,9 @@
 
 #include "../../include/olpe.h"
 #include "olpe_internal.h"
+#include "olpe_reduce.h"
 
+using olpe::block_sum;
 using olpe::set_err;
 
 namespace {
@@ -172,18 +174,6 @@ __global__ __launch_bounds__(kThreads) void fold_cols_kernel(const double *__res
   m2[o] = qa;
 }
 
-__device__ double block_sum(double v, double *red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = kThreads / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-
 // stage 1: block b reduces walkers [b*kWalkersPerBlock, ...) of every column into
 // part[q][col][b], q = 0: sum of means, 1: sum of M2, 2: sum of (mean - centre)^2
 // (centre may be NULL: block 2 is then 0), 3 / 4: tries / accepts (np columns)
@@ -208,9 +198,9 @@ __global__ __launch_bounds__(kThreads) void summary_stage1(
       const double d = m - ck;
       d2 = fma(d, d, d2);
     }
-    a = block_sum(a, red);
-    q = block_sum(q, red);
-    d2 = block_sum(d2, red);
+    a = block_sum<kThreads>(a, red);
+    q = block_sum<kThreads>(q, red);
+    d2 = block_sum<kThreads>(d2, red);
     if (threadIdx.x == 0) {
       part[((size_t)0 * ps + k) * nblk + b] = a;
       part[((size_t)1 * ps + k) * nblk + b] = q;
@@ -229,17 +219,6 @@ __global__ __launch_bounds__(kThreads) void summary_stage1(
   __syncthreads();
   double *pc = part + (size_t)3 * ps * nblk;
   for (int i = threadIdx.x; i < 2 * np; i += kThreads) pc[(size_t)i * nblk + b] = (double)cnt[i];
-}
-
-// stage 2: one block per output column, the blocks' partials in a fixed order
-__global__ __launch_bounds__(kThreads) void summary_stage2(const double *__restrict__ part,
-                                                           int nblk, double *__restrict__ out) {
-  __shared__ double red[kThreads];
-  const double *p = part + (size_t)blockIdx.x * nblk;
-  double a = 0.0;
-  for (int b = threadIdx.x; b < nblk; b += kThreads) a += p[b];
-  a = block_sum(a, red);
-  if (threadIdx.x == 0) out[blockIdx.x] = a;
 }
 
 int ensure_moments(olpe_ctx *c) {
@@ -304,8 +283,9 @@ int olpe_moments_local(olpe_ctx *c, const double *d_centre, double *d_out) {
                      c->d_mm2, d_centre, c->d_tries, c->d_acc, (long long)c->W, c->ps, c->np,
                      nblk, c->d_mpart);
   HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(summary_stage2, dim3((unsigned)cols), dim3(kThreads), 0, c->stream,
-                     c->d_mpart, nblk, d_out + 2);
+  // one block per output column, the blocks' partials in a fixed order
+  hipLaunchKernelGGL(olpe::reduce_stage2_kernel<kThreads>, dim3((unsigned)cols), dim3(kThreads),
+                     0, c->stream, c->d_mpart, nblk, d_out + 2);
   HIPCHK(hipGetLastError());
   return OLPE_OK;
 }

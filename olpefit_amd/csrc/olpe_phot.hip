@@ -51,28 +51,20 @@
 #include <vector>
 
 #include "../../include/olpe.h"
-#include "olpe_fold.h"
 #include "olpe_internal.h"
+#include "olpe_reduce.h"
 #include "olpe_select.h"
+#include "olpe_store.h"
 
 #pragma clang fp contract(off)
 
 using namespace olpe;
 
-struct olpe_phot : FoldBase {
-  int variant = 2;            // sources
-  int ps = 17;
+// the store holds Q planes; d_part [Q][4][nblk] (sum; count, min, max as words), d_out [Q][4],
+// d_words [1] next key
+struct olpe_phot : SampleStore {
   int Q = 7;
   double pixscale = 0;
-  long long W = 0, cap = 0;   // walkers, row capacity per walker
-  long long rows = 0;         // rows folded per walker
-  double *d_store = nullptr;  // [Q][cap * W]
-  double *d_part = nullptr;   // [Q][4][nblk] reduction partials (sum; count, min, max as words)
-  double *d_out = nullptr;    // [Q][4] reduction results
-  unsigned long long *d_words = nullptr;  // [0] unusable rows, [1] next key
-  unsigned long long *d_hist = nullptr;   // [kSelBins]
-  double *d_stage = nullptr;  // upload staging of fold_rows
-  size_t stage_cap = 0;
 };
 
 namespace {
@@ -159,35 +151,6 @@ __global__ __launch_bounds__(kThreads) void phot_fold_kernel(
   if (nbad) atomicAdd(bad, (unsigned long long)nbad);
 }
 
-// fixed-order trees over the block (every thread takes part)
-__device__ double block_sum(double v, double *red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = kThreads / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-
-// op 0: sum, 1: min, 2: max (integers: the same whatever the order)
-__device__ unsigned long long block_word(unsigned long long v, int op, unsigned long long *red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = kThreads / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) {
-      const unsigned long long a = red[threadIdx.x], b = red[threadIdx.x + o];
-      red[threadIdx.x] = op == 0 ? a + b : op == 1 ? (b < a ? b : a) : (b > a ? b : a);
-    }
-    __syncthreads();
-  }
-  const unsigned long long r = red[0];
-  __syncthreads();
-  return r;
-}
-
 struct Means {
   double m[kMaxQ];
 };
@@ -222,10 +185,10 @@ __global__ __launch_bounds__(kThreads) void phot_reduce_stage1(
     mn = k < mn ? k : mn;
     mx = k > mx ? k : mx;
   }
-  const double ts = block_sum(s, red);
-  const unsigned long long tc = block_word(cnt, 0, redw);
-  const unsigned long long tn = block_word(mn, 1, redw);
-  const unsigned long long tx = block_word(mx, 2, redw);
+  const double ts = block_sum<kThreads>(s, red);
+  const unsigned long long tc = block_word<kThreads, WordSum>(cnt, redw);
+  const unsigned long long tn = block_word<kThreads, WordMin>(mn, redw);
+  const unsigned long long tx = block_word<kThreads, WordMax>(mx, redw);
   if (threadIdx.x == 0) {
     double *p = part + (size_t)blockIdx.y * 4 * nblk + blockIdx.x;
     unsigned long long *pw = reinterpret_cast<unsigned long long *>(p);
@@ -253,10 +216,10 @@ __global__ __launch_bounds__(kThreads) void phot_reduce_stage2(const double *__r
     mn = l < mn ? l : mn;
     mx = h > mx ? h : mx;
   }
-  const double ts = block_sum(s, red);
-  const unsigned long long tc = block_word(cnt, 0, redw);
-  const unsigned long long tn = block_word(mn, 1, redw);
-  const unsigned long long tx = block_word(mx, 2, redw);
+  const double ts = block_sum<kThreads>(s, red);
+  const unsigned long long tc = block_word<kThreads, WordSum>(cnt, redw);
+  const unsigned long long tn = block_word<kThreads, WordMin>(mn, redw);
+  const unsigned long long tx = block_word<kThreads, WordMax>(mx, redw);
   if (threadIdx.x == 0) {
     double *o = out + (size_t)blockIdx.x * 4;
     unsigned long long *ow = reinterpret_cast<unsigned long long *>(o);
@@ -304,11 +267,6 @@ int launch_fold(olpe_phot *a, hipStream_t stream, const double *src, long long s
   return OLPE_OK;
 }
 
-int full(const olpe_phot *a, long long more) {
-  return set_err(OLPE_ESTATE, "sample store full: %lld + %lld rows per walker, capacity %lld",
-                 a->rows, more, a->cap);
-}
-
 }  // namespace
 
 extern "C" {
@@ -323,10 +281,8 @@ int olpe_phot_create(int device, int variant, int ps, double pixscale, long long
     return set_err(OLPE_EINVAL, "PS %d: the %d-source planes read columns up to %d", ps, variant,
                    need - 1);
   if (!isfinite(pixscale)) return set_err(OLPE_EINVAL, "non-finite pixscale");
-  if (walkers < 1 || row_cap < 1 || walkers > (65535ll * kTW) || row_cap > 0x7fffffffll ||
-      walkers > (1ll << 40) / row_cap)
-    return set_err(OLPE_EINVAL, "walkers %lld x row capacity %lld", walkers, row_cap);
   int rc;
+  if ((rc = store_geometry(walkers, row_cap, kTW))) return rc;
   if ((rc = open_device(device))) return rc;
   olpe_phot *a = new olpe_phot;
   a->variant = variant;
@@ -370,48 +326,30 @@ int olpe_phot_fold_ctx(olpe_phot *a, olpe_ctx *c, int row_step) {
   if ((rc = fold_check(a, c))) return rc;
   // rows 0, row_step, ... of the chain [W][nrec][PS]: indexing only
   const long long nr = (c->chain_rows + row_step - 1) / row_step;
-  if (a->rows + nr > a->cap) return full(a, nr);
+  if ((rc = store_room(a, nr))) return rc;
   HIPCHK(hipSetDevice(a->device));
-  fold_mark(a, c);
-  if (nr == 0) return OLPE_OK;
-  if ((rc = fold_enter(a, c))) return rc;
-  if ((rc = launch_fold(a, c->stream, c->d_chain, c->chain_rows * c->ps,
-                        (long long)row_step * c->ps, nr)))
+  if ((rc = fold_run(a, c, nr > 0, [&](hipStream_t s) {
+         return launch_fold(a, s, c->d_chain, c->chain_rows * c->ps, (long long)row_step * c->ps,
+                            nr);
+       })))
     return rc;
-  if ((rc = fold_leave(a, c))) return rc;
   a->rows += nr;
   return OLPE_OK;
 }
 
 int olpe_phot_fold_rows(olpe_phot *a, const double *rows, long long nrows) {
   if (!a || nrows < 0 || (nrows > 0 && !rows)) return set_err(OLPE_EINVAL, "bad argument");
-  if (a->rows + nrows > a->cap) return full(a, nrows);
-  if (nrows == 0) return OLPE_OK;
-  HIPCHK(hipSetDevice(a->device));
   int rc;
-  if ((rc = wait_pending(a))) return rc;
-  // whole rows travel, [rows][W][PS], in pieces of at most 64 MiB
+  if ((rc = store_room(a, nrows))) return rc;
+  if (nrows == 0) return OLPE_OK;
+  // whole rows travel, [rows][W][PS]
   const long long per_row = a->W * a->ps;
-  const long long chunk = std::max(1ll, std::min(nrows, (long long)(1 << 23) / per_row));
-  if ((rc = grow((void **)&a->d_stage, &a->stage_cap, (size_t)(chunk * per_row) * 8,
-                 "the row upload")))
-    return rc;
-  for (long long r0 = 0; r0 < nrows; r0 += chunk) {
-    const long long nr = std::min(chunk, nrows - r0);
-    HIPCHK(hipMemcpyAsync(a->d_stage, rows + (size_t)r0 * per_row, (size_t)(nr * per_row) * 8,
-                          hipMemcpyHostToDevice, a->stream));
-    if ((rc = launch_fold(a, a->stream, a->d_stage, a->ps, per_row, nr))) return rc;
-    HIPCHK(hipStreamSynchronize(a->stream));   // d_stage is reused
-    a->rows += nr;
-  }
-  return OLPE_OK;
+  return store_upload(
+      a, nrows, per_row, [&](long long r0, long long) { return rows + (size_t)r0 * per_row; },
+      [&](long long nr) { return launch_fold(a, a->stream, a->d_stage, a->ps, per_row, nr); });
 }
 
-int olpe_phot_rows(olpe_phot *a, long long *rows) {
-  if (!a || !rows) return set_err(OLPE_EINVAL, "NULL argument");
-  *rows = a->rows;
-  return OLPE_OK;
-}
+int olpe_phot_rows(olpe_phot *a, long long *rows) { return store_rows(a, rows); }
 
 int olpe_phot_unusable(olpe_phot *a, long long *n) {
   if (!a || !n) return set_err(OLPE_EINVAL, "NULL argument");
@@ -437,7 +375,6 @@ int olpe_phot_finalize(olpe_phot *a, const double *probs, int nprobs, double *ou
   int rc;
   if ((rc = wait_pending(a))) return rc;
   const long long n = a->rows * a->W;
-  const size_t N = (size_t)a->W * a->cap;
   const int len = OLPE_PHOT_LEN(nprobs);
   const double nan_ = nan("");
   Means mean = {};
@@ -468,26 +405,16 @@ int olpe_phot_finalize(olpe_phot *a, const double *probs, int nprobs, double *ou
       o[2] = sqrt(s2[q].sum / fn);
     }
     if (nprobs == 0) continue;
-    const double *x = a->d_store + (size_t)q * N;
-    SelRank r[kSelMaxRanks];
-    bool up[kSelMaxRanks];
-    for (int i = 0; i < nprobs; ++i) {
-      const double vi = (fn - 1.0) * probs[order[i]];      // np.percentile's virtual index
-      r[i].k = (long long)floor(vi);
-      up[i] = ceil(vi) != floor(vi);
-    }
+    double vi[kSelMaxRanks];                               // np.percentile's virtual indices
+    unsigned long long lo[kSelMaxRanks], hi[kSelMaxRanks];
+    for (int i = 0; i < nprobs; ++i) vi[i] = (fn - 1.0) * probs[order[i]];
     int passes = 0;
-    if ((rc = select_ranks(a->stream, a->d_hist, x, n, cnt, s1[q].kmin, s1[q].kmax, r, nprobs,
-                           &passes)))
+    if ((rc = select_brackets(a->stream, a->d_hist, a->d_words + 1, store_plane(a, q), n, cnt,
+                              s1[q].kmin, s1[q].kmax, vi, nprobs, lo, hi, &passes)))
       return rc;
     for (int i = 0; i < nprobs; ++i) {
-      unsigned long long hi = r[i].key;
-      // keys <= r.key: those below it and its copies
-      if (up[i] && (unsigned long long)(r[i].k + 1) >= r[i].below + r[i].equal &&
-          (rc = select_next(a->stream, a->d_words + 1, x, n, r[i].key, s1[q].kmax, &hi, &passes)))
-        return rc;
-      o[6 + 2 * order[i]] = okey_inv(r[i].key);
-      o[7 + 2 * order[i]] = okey_inv(hi);
+      o[6 + 2 * order[i]] = okey_inv(lo[i]);
+      o[7 + 2 * order[i]] = okey_inv(hi[i]);
     }
     o[5] = (double)passes;
   }
@@ -500,9 +427,7 @@ int olpe_phot_samples(olpe_phot *a, int plane, double *out) {
   HIPCHK(hipSetDevice(a->device));
   int rc;
   if ((rc = drain(a))) return rc;
-  const size_t n = (size_t)a->rows * a->W, N = (size_t)a->W * a->cap;
-  if (n) HIPCHK(hipMemcpy(out, a->d_store + (size_t)plane * N, n * 8, hipMemcpyDeviceToHost));
-  return OLPE_OK;
+  return store_read(a, plane, out);
 }
 
 int olpe_phot_reset(olpe_phot *a) {

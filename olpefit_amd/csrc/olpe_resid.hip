@@ -628,17 +628,14 @@ int olpe_resid_fold_ctx(olpe_resid *r, olpe_ctx *c, int row_step, int walker_ste
   int rc;
   if ((rc = fold_check(r, c))) return rc;
   HIPCHK(hipSetDevice(r->device));
-  fold_mark(r, c);
   // rows 0, row_step, ... of walkers 0, walker_step, ... of the chain [W][nrec][PS],
   // walker-major: indexing only
   const long long nr = (c->chain_rows + row_step - 1) / row_step;
   const long long nw = ((long long)c->W + walker_step - 1) / walker_step;
-  if (nr == 0 || nw == 0) return OLPE_OK;
-  if ((rc = fold_enter(r, c))) return rc;
   const RowMap m{c->d_chain, nr, (long long)walker_step * c->chain_rows * c->ps,
                  (long long)row_step * c->ps};
-  if ((rc = launch_fold(r, c->stream, m, nr * nw))) return rc;
-  return fold_leave(r, c);
+  return fold_run(r, c, nr > 0 && nw > 0,
+                  [&](hipStream_t s) { return launch_fold(r, s, m, nr * nw); });
 }
 
 int olpe_resid_fold_rows(olpe_resid *r, const double *rows, long long nsamples) {

@@ -10,11 +10,13 @@
 // prefix (per workgroup in LDS, merged with integer atomics), the host picks the bin
 // that holds the rank.  Several ranks of one array share a pass for as long as they fall
 // into the same bins (select_ranks); the key that follows a found one costs one more
-// read (select_next), which is how a neighbouring rank is had without a second descent.
+// read (select_next), which is how a neighbouring rank is had without a second descent
+// (select_brackets: the pair of ranks around a virtual index).
 // Integer work only: the result does not depend on the order of anything.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <math.h>
 #include <string.h>
 
 #include <algorithm>
@@ -22,6 +24,7 @@
 
 #include "../../include/olpe.h"
 #include "olpe_internal.h"
+#include "olpe_reduce.h"
 
 namespace olpe {
 
@@ -70,21 +73,15 @@ static __global__ __launch_bounds__(kSelThreads) void select_hist_kernel(
 static __global__ __launch_bounds__(kSelThreads) void select_next_kernel(
     const double *__restrict__ x, long long n, unsigned long long key, unsigned long long kmax,
     unsigned long long *__restrict__ out) {
-  __shared__ unsigned long long lo[kSelThreads];
+  __shared__ unsigned long long red[kSelThreads];
   unsigned long long m = ~0ull;
   for (long long i = (long long)blockIdx.x * kSelThreads + threadIdx.x; i < n;
        i += (long long)gridDim.x * kSelThreads) {
     const unsigned long long k = okey(x[i]);
     if (k > key && k <= kmax && k < m) m = k;
   }
-  lo[threadIdx.x] = m;
-  __syncthreads();
-  for (int o = kSelThreads / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o && lo[threadIdx.x + o] < lo[threadIdx.x])
-      lo[threadIdx.x] = lo[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) atomicMin(out, lo[0]);
+  m = block_word<kSelThreads, WordMin>(m, red);
+  if (threadIdx.x == 0) atomicMin(out, m);
 }
 
 inline unsigned select_grid(long long n) {
@@ -172,6 +169,31 @@ inline int select_next(hipStream_t stream, unsigned long long *d_word, const dou
   HIPCHK(hipMemcpyAsync(out, d_word, 8, hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
   if (passes) ++*passes;
+  return OLPE_OK;
+}
+
+// The brackets of the order statistics at the virtual indices vidx[0 .. nr) (ascending, each
+// in [0, n_in - 1], as np.percentile's (n - 1) p): lo[i] / hi[i] are the keys at ranks
+// floor(v) and ceil(v).  One shared descent for the lower ranks; an upper rank that is not a
+// copy of its lower one costs one more read.  d_hist as for select_ranks, d_word as for
+// select_next; `passes` counts the reads of x.
+inline int select_brackets(hipStream_t stream, unsigned long long *d_hist,
+                           unsigned long long *d_word, const double *x, long long n,
+                           unsigned long long n_in, unsigned long long kmin,
+                           unsigned long long kmax, const double *vidx, int nr,
+                           unsigned long long *lo, unsigned long long *hi, int *passes) {
+  SelRank r[kSelMaxRanks];
+  for (int i = 0; i < nr && i < kSelMaxRanks; ++i) r[i].k = (long long)floor(vidx[i]);
+  int rc;
+  if ((rc = select_ranks(stream, d_hist, x, n, n_in, kmin, kmax, r, nr, passes))) return rc;
+  for (int i = 0; i < nr; ++i) {
+    lo[i] = hi[i] = r[i].key;
+    // keys <= r.key: those below it and its copies
+    if (ceil(vidx[i]) != floor(vidx[i]) &&
+        (unsigned long long)(r[i].k + 1) >= r[i].below + r[i].equal &&
+        (rc = select_next(stream, d_word, x, n, r[i].key, kmax, &hi[i], passes)))
+      return rc;
+  }
   return OLPE_OK;
 }
 

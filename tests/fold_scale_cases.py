@@ -9,7 +9,8 @@ Every fold caps its grid; below the cap a workgroup takes one unit and its loop 
     cov_fold_kernel      2048 workgroups over W ceil(N / tile) tiles of one walker's rows
     acf_fold_kernel      1024 workgroups over series x ceil(N / T) time tiles
     select_*_kernel      1024 x 256 threads, grid-stride over the samples
-    *_reduce_stage2      256 threads over the ceil(n / 4096) stage-1 partials
+    reduce_stage2_kernel 256 threads over the ceil(n / 4096) stage-1 partials (olpe_reduce.h:
+                         astrometry, moments), as phot_reduce_stage2
     astrom_correct       4096 x 256 threads, grid-stride
     corner fold_rows     upload pieces of 2^18 samples
     corner launch_fold   at most 2048 / tiles chunks of the samples

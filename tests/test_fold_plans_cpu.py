@@ -51,8 +51,13 @@ def test_the_caps_are_the_sources():
         assert const(text, "kThreads") == fc.REDUCE_THREADS, name
         assert const(text, "kThreads") * const(text, "kPer") == fc.REDUCE_CHUNK, name
         assert re.search(r"constexpr long long kChunk\s*=\s*kThreads \* kPer;", text), name
-        assert re.search(r"for \(int b = threadIdx\.x; b < nblk; b \+= kThreads\)", text), name
-    astrom = source("olpe_astrom.hip")
+    # stage 2: phot's own kernel, and the shared one (olpe_reduce.h) astrom launches
+    assert re.search(r"for \(int b = threadIdx\.x; b < nblk; b \+= kThreads\)",
+                     source("olpe_phot.hip"))
+    red, astrom = source("olpe_reduce.h"), source("olpe_astrom.hip")
+    assert re.search(r"for \(int b = threadIdx\.x; b < nblk; b \+= T\)", red)
+    assert "__launch_bounds__(T) void reduce_stage2_kernel(" in red
+    assert "hipLaunchKernelGGL(reduce_stage2_kernel<kThreads>, dim3(nv), dim3(kThreads)," in astrom
     m = re.search(r"cgrid = \(unsigned\)std::min<long long>\(\(n \+ kThreads - 1\) / kThreads, "
                   r"(\d+)\)", astrom)
     assert m and int(m.group(1)) * const(astrom, "kThreads") == fc.CORRECT_THREADS

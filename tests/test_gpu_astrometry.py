@@ -158,7 +158,8 @@ def test_medians_and_parity_past_the_grid_caps(lib_loaded, shape):
     """Variant 2 with the tables at sample counts past the caps (tests/fold_scale_cases.py):
     700 x 400 = 280,000 samples give the select's 1024 x 256 threads a second trip of their
     grid-stride loops; 1025 x 1024 = 1,049,600 are past astrom_correct_kernel's 4096 x 256
-    threads and make 257 stage-1 partials for the 256 threads of astrom_reduce_stage2.  (The
+    threads and make 257 stage-1 partials for the 256 threads of reduce_stage2_kernel
+    (olpe_reduce.h).  (The
     NumPy restatement of the larger case takes 0.3 s with the tables, so they stay.)"""
     W, rows, tab = fc.ASTROM[shape]
     chain = make_chain(W, rows, 2, seed=31)
