@@ -156,6 +156,57 @@ int olpe_last_units(olpe_ctx *ctx, int *units);
  * out[1] = total wave-time spent waiting (ns).  Diagnostics; build-specific. */
 int olpe_unit_stats(olpe_ctx *ctx, long long *out);
 
+/* --- jump widths (apf_step2.py:234; 3body/apf_step2_3body.py:220-238) --------------
+ * The reference's one tuning knob: the scale of proposal() (:63-65, loc + w gauss()) and
+ * of logproposal() (:66-70, 10**(log10 loc + w gauss()), w in dex), one per proposable
+ * parameter, edited by hand in the source.  Here each context carries its own [P] on the
+ * device; the defaults are the reference's. */
+/* The largest width a log-proposed parameter takes.  The FAST form of logproposal is
+ * cur * e^(w g ln 10), the exponential by the table exp (ExpTab) once |w g ln 10| >=
+ * 1/16; ExpTab is tested on [-1000, 710] and returns inf beyond 710.  The polar method
+ * forms g = x sqrt(-2 ln(r2) / r2) with r2 = x1^2 + x2^2 and x1, x2 multiples of 2^-52, so
+ * |g| <= sqrt(-2 ln r2) <= sqrt(208 ln 2) = 12.0073 (r2 >= 2^-104).  Hence the exponent
+ * stays inside the domain for w <= 710 / (12.0073 ln 10) = 25.68; the entry point takes
+ * up to 25 (|w g ln 10| <= 691.2). */
+#define OLPE_LOG_WIDTH_MAX 25.0
+/* Replace the context's widths with w[P]; w == NULL restores the defaults.  Ordered on the
+ * context's stream without a host wait (w is copied before the call returns): every launch
+ * enqueued afterwards runs with the new widths, none enqueued before.  OLPE_EINVAL, with
+ * the widths unchanged, for an entry that is not finite and > 0 and for a log-proposed
+ * parameter (lognorm, apf_step2.py:217; 3body :295) above OLPE_LOG_WIDTH_MAX. */
+int olpe_widths_set(olpe_ctx *ctx, const double *w);
+/* The widths in force once the context's stream has drained into out[P] (synchronises). */
+int olpe_widths_get(olpe_ctx *ctx, double *out);
+
+/* --- acceptance-rate tuner of the jump widths --------------------------------------
+ * What a user of the reference does by hand between runs (read {rank}_acceptance.txt,
+ * apf_step2.py:362-365, edit :234), done on the device between launches from the
+ * ensemble's own counters, without a host round trip.  Build-specific.
+ * olpe_tune_begin: needs 0 < target < 1, gain > 0 and gain * target < 1 (so that every
+ * factor below is positive), else OLPE_EINVAL; OLPE_ESTATE before olpe_seed.  Sets the
+ * step count k = 0 and takes the baseline: the 64-bit integer sums over walkers of
+ * tries[.][j] and accepts[.][j].
+ * olpe_tune_step: enqueues on the context's stream, without synchronising,
+ *   1. the same sums again (integer: exact in any order);
+ *   2. the signed deltas dT_j, dA_j against the previous sums, which they replace;
+ *   3. k <- k + 1;
+ *   4. for every j with dT_j > 0:  a = double(dA_j) / double(dT_j),
+ *      f = 1 + g_k (a - target) with g_k = gain / sqrt(k) (formed on the host),
+ *      w_j <- min(max(w_j f, default_j / 1024), default_j * 64); a parameter with
+ *      dT_j <= 0 keeps its width exactly.  Each operation is one correctly rounded IEEE
+ *      double operation in this order (no contraction, no fast division);
+ *   5. appends (dT, dA, the new widths) to a device log of OLPE_TUNE_LOG steps.
+ * OLPE_ESTATE without olpe_tune_begin, or with the log full.
+ * olpe_tune_get: synchronises; *steps = k, and the log oldest first into dT, dA, widths
+ * ([k][P] each; any may be NULL; OLPE_TUNE_LOG rows are always enough).  The log of an
+ * ended session stays readable until the next olpe_tune_begin.
+ * olpe_tune_end: ends the session; the widths stay as they are. */
+#define OLPE_TUNE_LOG 256
+int olpe_tune_begin(olpe_ctx *ctx, double target, double gain);
+int olpe_tune_step(olpe_ctx *ctx);
+int olpe_tune_get(olpe_ctx *ctx, int *steps, long long *dT, long long *dA, double *widths);
+int olpe_tune_end(olpe_ctx *ctx);
+
 /* --- chain files (apf_step2.py:342-360; 3body/apf_step2_3body.py:381-399) ---------
  * Host-only (no GPU needed).  Rows are formatted as the reference's csv.writer writes
  * a list of float rows: repr() of each value (shortest round-trip digits, fixed

@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get("OLPE_LIB", os.path.join(HERE, "libolpe.so"))
 OK, EINVAL, EHIP, ENOMEM, ESTATE, ECOMM, EIO = 0, -1, -2, -3, -4, -5, -6
 DTYPE_F32, DTYPE_F64 = 0, 1
 EVAL_EXACT, EVAL_FAST = 0, 1
+LOG_WIDTH_MAX = 25.0      # OLPE_LOG_WIDTH_MAX
+TUNE_LOG = 256            # OLPE_TUNE_LOG
 
 
 class OlpeError(RuntimeError):
@@ -65,6 +67,12 @@ SIGNATURES = {
     "olpe_kernel_times": (_i, [_P, _i, _pd]),
     "olpe_last_units": (_i, [_P, C.POINTER(C.c_int)]),
     "olpe_unit_stats": (_i, [_P, _pll]),
+    "olpe_widths_set": (_i, [_P, _pd]),
+    "olpe_widths_get": (_i, [_P, _pd]),
+    "olpe_tune_begin": (_i, [_P, _d, _d]),
+    "olpe_tune_step": (_i, [_P]),
+    "olpe_tune_get": (_i, [_P, C.POINTER(_i), _pll, _pll, _pd]),
+    "olpe_tune_end": (_i, [_P]),
     "olpe_csv_format": (_i, [_pd, _ll, _i, _i, C.c_char_p, C.c_size_t,
                              C.POINTER(C.c_size_t)]),
     "olpe_csv_write_chains": (_i, [C.POINTER(C.c_char_p), _pd, _i, _ll, _i, _i, _i]),

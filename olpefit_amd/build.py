@@ -14,7 +14,8 @@ LIB = os.path.join(HERE, "libolpe.so")
 SOURCES = [os.path.join(CSRC, f) for f in ("olpe.hip", "olpe_comm.hip", "olpe_moments.hip",
                                             "olpe_astrom.hip", "olpe_csv.cpp",
                                             "olpe_corner.hip", "olpe_resid.hip",
-                                            "olpe_acf.hip", "olpe_phot.hip", "olpe_cov.hip")]
+                                            "olpe_acf.hip", "olpe_phot.hip", "olpe_cov.hip",
+                                            "olpe_tune.hip")]
 DEPS = SOURCES + [os.path.join(CSRC, f) for f in ("olpe_device.h", "olpe_internal.h",
                                                  "olpe_fold.h", "olpe_select.h", "olpe_reduce.h",
                                                  "olpe_store.h", "exp_table.h",

@@ -269,6 +269,50 @@ class Sampler:
         check(self._lib.olpe_last_units(self._ctx, C.byref(v)))
         return v.value
 
+    # -- jump widths and their tuner (apf_step2.py:234; 3body :220-238) -----------
+    def set_widths(self, w=None):
+        """The proposal widths [P] of every launch enqueued from here on (no host sync);
+        ``None`` restores the reference's.  Raises (OLPE_EINVAL), with the widths
+        unchanged, on an entry that is not finite and > 0 or a log-proposed parameter
+        above ``_lib.LOG_WIDTH_MAX`` dex."""
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float64)
+            if w.shape != (self.np_,):
+                raise ValueError(f"widths must have {self.np_} entries")
+        check(self._lib.olpe_widths_set(self._ctx, _dptr(w)))
+
+    def get_widths(self):
+        """The widths in force once everything enqueued has run (synchronises)."""
+        out = np.empty(self.np_)
+        check(self._lib.olpe_widths_get(self._ctx, _dptr(out)))
+        return out
+
+    def tune_begin(self, target=0.44, gain=2.0):
+        """Start a tuning session (olpe_tune_begin): the baseline of the ensemble's
+        tries / accepts sums; needs 0 < target < 1, gain > 0, gain * target < 1."""
+        check(self._lib.olpe_tune_begin(self._ctx, float(target), float(gain)))
+
+    def tune_step(self):
+        """Adapt every width from the acceptance rate since the last step (or the
+        baseline), on the device behind the launches enqueued so far (no host sync)."""
+        check(self._lib.olpe_tune_step(self._ctx))
+
+    def tune_history(self):
+        """(dT [k, P] int64, dA [k, P] int64, widths [k, P]) of the k steps of the
+        current (or last ended) session, oldest first (synchronises)."""
+        k = C.c_int(0)
+        dT = np.zeros((_lib.TUNE_LOG, self.np_), dtype=np.int64)
+        dA = np.zeros((_lib.TUNE_LOG, self.np_), dtype=np.int64)
+        w = np.zeros((_lib.TUNE_LOG, self.np_))
+        check(self._lib.olpe_tune_get(self._ctx, C.byref(k), dT.ctypes.data_as(_lib._pll),
+                                      dA.ctypes.data_as(_lib._pll), _dptr(w)))
+        k = k.value
+        return dT[:k].copy(), dA[:k].copy(), w[:k].copy()
+
+    def tune_end(self):
+        """End the session; the widths stay as the last step left them."""
+        check(self._lib.olpe_tune_end(self._ctx))
+
     # -- devices ----------------------------------------------------------------
     @staticmethod
     def device_count() -> int:

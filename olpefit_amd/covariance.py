@@ -22,11 +22,12 @@ of a converged chain, or the column means, keeps that factor at about two.
 
 Everything after the sums is plain NumPy on a state dict and needs no GPU: ``covariance``,
 ``correlation``, ``rebase``, ``error_ellipse``, ``conditional_sigma``, ``mpsrf``,
-``table_lines``.
+``table_lines``, and ``proposal_widths``, which turns the conditional widths into the
+sampler's proposal widths (``Sampler.set_widths``, step 2's ``--widths``).
 
 Not covered: sky-frame ellipses (rotation, distortion and refraction are not applied) and a
 separation / position-angle correlation, a collective over the state, per-walker covariance
-matrices, feeding the conditional widths back into the sampler's proposal widths.
+matrices.
 """
 from __future__ import annotations
 
@@ -192,6 +193,39 @@ def conditional_sigma(cov, cols=None):
         cond = float(np.linalg.cond(R))
     return {"cols": cols, "sigma_marginal": sd, "sigma_cond": sd * eff, "efficiency": eff,
             "condition": cond}
+
+
+def proposal_widths(state, nsrc: int, scale: float = 2.38):
+    """Proposal widths [P] for the sampler (``Sampler.set_widths``, ``--widths``) from the
+    conditional widths of a state whose first P columns are the proposable parameters (the
+    chi^2 column, and any after it, is left out of the inverse).  One parameter moves per
+    step, given all the others, so the scale of its move is its conditional width: a proposed
+    parameter takes ``scale`` sigma_cond (2.38: the one-dimensional optimum of a Gaussian
+    target, Gelman, Roberts & Gilks 1996), a log-proposed one ``scale`` sigma_cond / (|mean|
+    ln 10), its width in dex about the mean p + S1 / n.  An entry whose sigma_cond is zero or
+    not finite (a constant column, too few rows), or whose value in dex is not finite, keeps
+    the default.  Host arithmetic, no GPU."""
+    from . import tune
+    w = tune.default_widths(nsrc)
+    P = w.size
+    if np.asarray(state["S2"]).shape[0] < P:
+        raise ValueError(f"a state of {np.asarray(state['S2']).shape[0]} columns for {P} parameters")
+    cov = np.array(covariance(state))
+    const = constant_columns(state)
+    cov[const, const] = np.nan                  # no variance to read: out of the inverse
+    sc = conditional_sigma(cov, range(P))["sigma_cond"]
+    mu = mean(state)[:P]
+    logp = set(tune.log_params(nsrc))
+    for j in range(P):
+        if not (np.isfinite(sc[j]) and sc[j] > 0.0):
+            continue
+        v = scale * sc[j]
+        if j in logp:
+            with np.errstate(divide="ignore", invalid="ignore"):
+                v = v / (abs(mu[j]) * np.log(10.0))
+        if np.isfinite(v) and v > 0.0:
+            w[j] = v
+    return w
 
 
 def mpsrf(state, between=None, cols=None):

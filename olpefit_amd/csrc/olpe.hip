@@ -44,8 +44,25 @@ __constant__ double c_widths3[19] = {0.01,  0.01,  0.3,   0.3,  0.3,   0.3,   0.
                                      0.09,  0.0025, 0.02, 0.02, 0.001, 0.0008, 0.002,
                                      0.002, 0.001, 0.001, 0.008, 0.01};
 
-template <int NSRC> __device__ __forceinline__ double width_of(int r) {
-  return NSRC == 2 ? c_widths2[r] : c_widths3[r];
+// The tables above are the defaults; a launch reads its context's own copy (olpe_ctx::
+// d_widths, filled from them by widths_default_kernel, changed by olpe_widths_set and the
+// tuner of olpe_tune.hip between launches, never during one).  In the FAST samplers each
+// work unit copies it into its wave slice (WaveSlice::OWD) with the walker's state, and the
+// step reads the drawn parameter's width from there, next to the parameter itself; the
+// EXACT samplers read it where the tables were read, by a scalar load through the constant
+// address space (the index is the drawn parameter, wave-uniform, and the buffer is constant
+// for the launch).  Each form is the faster one for its samplers.
+__device__ __forceinline__ double width_of(const double *widths, int r) {
+  return ((const __attribute__((address_space(4))) double *)widths)[r];
+}
+
+// the context's widths (and the tuner's clamps' base) from the default tables
+__global__ void widths_default_kernel(int nsrc, double *w, double *wdef) {
+  const int j = threadIdx.x;
+  if (j >= (nsrc == 2 ? 16 : 19)) return;
+  const double v = nsrc == 2 ? c_widths2[j] : c_widths3[j];
+  w[j] = v;
+  if (wdef) wdef[j] = v;
 }
 
 struct GibbsArgs {
@@ -70,6 +87,7 @@ struct GibbsArgs {
   double *chain;       // [W][nrows][PS]
   long long accept_min;
   double *trace;       // [W][n_iters][6] or null
+  const double *widths; // [NP] jump widths of this launch (constant while it runs)
   // walker queue: null = one walker per wave at blockIdx*WPB + wave; otherwise each
   // wave takes work units qbase.. from the counter until it passes W * units
   // (persistent grid)
@@ -110,12 +128,12 @@ template <int NP> struct WaveSlice {
   static constexpr int U32 = 2 * NP;                         // 8-byte multiple for NP 16/19
   static constexpr int PS = NP + 1;
   static constexpr int NSRC = NP == 16 ? 2 : 3;
-  // doubles: params[PS] | T1[5] T2[5] | C1[3] C2[3] | pending T[5] C[3] | PS unused (OPR:
-  // the proposal vector of the per-step descriptor rebuild, gone with it);
+  // doubles: params[PS] | T1[5] T2[5] | C1[3] C2[3] | pending T[5] C[3] | the launch's
+  // jump widths [NP] (OWD, FAST samplers; one double spare);
   // a shape set's T holds cos^2, sin^2, sin 2theta and (FAST) 1/sigma_x^2, 1/sigma_y^2
   static constexpr int OT1 = PS, OT2 = PS + 5, OC1 = PS + 10, OC2 = PS + 13;
   static constexpr int OPT = PS + 16, OPC = PS + 21;
-  static constexpr int OPR = PS + 24;
+  static constexpr int OWD = PS + 24;
   static constexpr int F64 = 2 * PS + 24;
   static constexpr int OMD = ((U32 * 4 + F64 * 8 + 15) & ~15);             // ModelDesc
   // col_coef [G][3], then (128 x 128) the pass-step factors exp(-64 b) [G]
@@ -442,6 +460,9 @@ void olpe_gibbs_kernel(GibbsArgs A) {
       s_acc[lane] = K()->accepts[(size_t)w * NP + lane];
     }
     if (lane < PS) st[lane] = K()->state[(size_t)w * PS + lane];
+    if constexpr (FAST) {
+      if (lane < NP) st[WS::OWD + lane] = K()->widths[lane];
+    }
     wave_sync();
     if (lane == 0) {
       const Trig t1 = make_trig<FAST>(st[L::T1]), t2 = make_trig<FAST>(st[L::T2]);
@@ -548,7 +569,9 @@ void olpe_gibbs_kernel(GibbsArgs A) {
       // proposal / logproposal (:63-70, :306-309): loc + scale*gauss
       // (read by every lane: nv is made uniform below, cur needs no readfirstlane)
       const double cur = st[r];
-      const double wr = width_of<NSRC>(r);
+      double wr;
+      if constexpr (FAST) wr = st[WS::OWD + r];
+      else wr = width_of(A.widths, r);
       double nv;
       if ((L::LOGMASK >> r) & 1u) {
         if constexpr (FAST) {
@@ -1140,6 +1163,15 @@ int ensure_ensemble(olpe_ctx *c, int W) {
 
 }  // namespace
 
+// the default tables into the context's widths (and, at creation, into the copy the tuner
+// clamps against), behind whatever the context's stream holds
+int olpe_widths_defaults(olpe_ctx *c, bool with_base) {
+  hipLaunchKernelGGL(widths_default_kernel, dim3(1), dim3(64), 0, c->stream, c->nsrc, c->d_widths,
+                     with_base ? c->d_wdef : nullptr);
+  HIPCHK(hipGetLastError());
+  return OLPE_OK;
+}
+
 extern "C" {
 
 int olpe_version(void) { return 101; }
@@ -1323,6 +1355,18 @@ int olpe_create(const void *image, int image_dtype, const void *pois2, double re
     olpe_destroy(c);
     return set_err(OLPE_EHIP, "hipMemcpy image: %s", hipGetErrorString(e2));
   }
+  // the jump widths: the device fills the context's copy, and the base of the tuner's
+  // clamps, from the default tables
+  c->logmask = nsrc == 2 ? Layout<2>::LOGMASK : Layout<3>::LOGMASK;
+  if ((rc = dev_alloc(&c->d_widths, (size_t)c->np)) || (rc = dev_alloc(&c->d_wdef, (size_t)c->np)) ||
+      (rc = olpe_widths_defaults(c, true))) {
+    olpe_destroy(c);
+    return rc;
+  }
+  if (hipStreamSynchronize(c->stream) != hipSuccess) {
+    olpe_destroy(c);
+    return set_err(OLPE_EHIP, "filling in the default jump widths failed");
+  }
   *out = c;
   return OLPE_OK;
 }
@@ -1335,7 +1379,8 @@ void olpe_destroy(olpe_ctx *c) {
   void *ptrs[] = {c->d_DE, c->d_DW, c->d_state, c->d_tries, c->d_acc,
                   c->d_mt, c->d_mtpos, c->d_gauss, c->d_hasg,  c->d_done,
                   c->d_chain, c->d_trace, c->d_scratch, c->d_scratch2, c->d_queue,
-                  c->d_gather, c->d_uflag, c->d_mmean, c->d_mm2, c->d_mpart, c->d_check};
+                  c->d_gather, c->d_uflag, c->d_mmean, c->d_mm2, c->d_mpart, c->d_check,
+                  c->d_widths, c->d_wdef, c->d_tune};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (auto &pair : c->ev)
@@ -1557,6 +1602,7 @@ int olpe_run(olpe_ctx *c, long long n_iters, long long burn_in, int record_strid
   a.chain = c->d_chain;
   a.accept_min = accept_min;
   a.trace = c->trace_on ? c->d_trace : nullptr;
+  a.widths = c->d_widths;
   hipEvent_t *ev = c->ev[c->launches % olpe_ctx::kRing];
   if (!ev[0] || !ev[1]) return set_err(OLPE_EHIP, "launch events were not created");
   HIPCHK(hipEventRecord(ev[0], c->stream));

@@ -63,6 +63,16 @@ struct olpe_ctx {
   int ring_wpb = 12;        // 128x128 FAST: the lockstep LDS-ring sampler's waves per
                             // workgroup, 0 = the L2-resident sampler (OLPE_RING)
   int stagger = 0;          // wave start offsets (always 0; see GibbsArgs)
+  // jump widths (apf_step2.py:234; 3body :220-238): d_widths [np] is what a launch reads,
+  // d_wdef [np] the defaults the device filled in from olpe.hip's tables (the tuner's
+  // clamps are multiples of them)
+  double *d_widths = nullptr, *d_wdef = nullptr;
+  uint32_t logmask = 0;         // bit j: parameter j is log-proposed (Layout::LOGMASK)
+  // the tuner's session (olpe_tune.hip): d_tune holds the sums now and before, then the log
+  void *d_tune = nullptr;
+  bool tune_on = false;
+  int tune_k = 0;               // steps taken in this session
+  double tune_target = 0, tune_gain = 0;
   // whole-run moments of the recorded rows (olpe_moments.hip): running mean / M2 per
   // walker and column, [ps][W]; mom_n rows folded per walker; mom_folded = the launch
   // whose rows were folded last (a launch is folded at most once)
@@ -100,6 +110,9 @@ int set_err(int code, const char *fmt, ...);
       return ::olpe::set_err(OLPE_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
 void olpe_comm_release(olpe_ctx *c);
+// the default jump widths into c->d_widths (with_base: into c->d_wdef too), a launch on
+// the context's stream (olpe.hip, where the default tables live)
+int olpe_widths_defaults(olpe_ctx *c, bool with_base);
 // the collectives' word buffer with its poisoned defaults (olpe_comm.hip; olpe_create)
 int olpe_comm_setup(olpe_ctx *c);
 // the buffers (and zeroing) of the per-column sums (olpe_moments.hip); then the sums over

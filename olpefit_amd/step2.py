@@ -26,7 +26,9 @@ all W walkers and the other ranks exit (``MPI_ENV``).  Added flags: ``--walkers`
 reference's MPI size), ``--seed``, ``--iters`` (fixed
 length instead of accept_min), ``--record-stride``, ``--gpus``, ``--exact``,
 ``--fixed-bkgd``, ``--chunk``, ``--mem-budget``, ``--checkpoint-secs``,
-``--checkpoint-every``, ``--resume``, ``--no-csv``, ``--npy``.
+``--checkpoint-every``, ``--resume``, ``--no-csv``, ``--npy``, and the proposal widths'
+``--widths`` and ``--tune-widths`` (with ``--tune-every``, ``--tune-target``,
+``--tune-gain``), which write ``proposal_widths.json`` beside the chain files.
 """
 from __future__ import annotations
 
@@ -40,7 +42,7 @@ import time
 
 import numpy as np
 
-from . import _lib, dist, fitsio, pipeline, step3
+from . import _lib, dist, fitsio, pipeline, step3, tune
 from .core import Sampler
 
 MAX_CHUNK = 20000          # iterations per launch when memory allows
@@ -114,6 +116,19 @@ def parse(argv, nsrc, variant="2"):
     ap.add_argument("--share-gpu", action="store_true",
                     help="one process per rank (torchrun): every rank on --device instead "
                          "of LOCAL_RANK's GPUs (a rehearsal on a one-GPU host)")
+    ap.add_argument("--widths", type=str, default=None, metavar="FILE",
+                    help="proposal widths from a widths file (olpefit_amd.tune) instead of the "
+                         "reference's (apf_step2.py:234); every rank reads the same file")
+    ap.add_argument("--tune-widths", type=int, default=0, metavar="T",
+                    help="adapt the proposal widths to the ensemble's acceptance rates over "
+                         "the first T iterations (within --burn-in), then freeze them; one "
+                         "GPU only (tune once, then hand the file to --widths)")
+    ap.add_argument("--tune-every", type=int, default=240, metavar="N",
+                    help="iterations per tuning launch (a multiple of 10 that divides T)")
+    ap.add_argument("--tune-target", type=float, default=0.44, metavar="A",
+                    help="acceptance rate the tuner steers every parameter to")
+    ap.add_argument("--tune-gain", type=float, default=2.0, metavar="G",
+                    help="the tuner's gain: step k scales a width by 1 + G / sqrt(k) (a - A)")
     ap.add_argument("--no-csv", action="store_true")
     ap.add_argument("--npy", action="store_true", help="also write {w}_chain.npy")
     ap.add_argument("--timing", action="store_true",
@@ -127,7 +142,39 @@ def parse(argv, nsrc, variant="2"):
         ap.error("apf_step2a runs one walker (it writes a single step2a.csv)")
     if args.walkers < 1 or args.record_stride < 1 or args.chunk < 0:
         ap.error("--walkers and --record-stride must be >= 1, --chunk >= 0")
+    T, N = args.tune_widths, args.tune_every
+    if T < 0:
+        ap.error("--tune-widths must be >= 0")
+    if T:
+        # the widths are frozen before the first recorded row: the chain files hold plain
+        # Metropolis-Hastings with fixed symmetric proposals
+        if T > args.burn_in:
+            ap.error(f"--tune-widths {T}: tuning ends within the burn-in (--burn-in {args.burn_in})")
+        if N < 10 or N % 10 or T % N:
+            ap.error(f"--tune-every {N}: a multiple of 10 that divides --tune-widths {T}")
+        if args.iters and T > (args.iters // 10) * 10:
+            ap.error(f"--tune-widths {T}: more than the run's --iters {args.iters}")
+        n_par = 16 if nsrc == 2 else 19
+        if not args.iters and args.accept_min > 0 and T > n_par * args.accept_min:
+            ap.error(f"--tune-widths {T}: the run may end before {n_par} x --accept-min "
+                     f"{args.accept_min} iterations, tuning must not pass them")
+        if not (0.0 < args.tune_target < 1.0 and args.tune_gain > 0.0
+                and args.tune_gain * args.tune_target < 1.0):
+            ap.error("--tune-target in (0, 1), --tune-gain > 0 and their product < 1")
+        err = tuning_needs_one_context(args, 1)
+        if err:
+            ap.error(err)
     return args
+
+
+def tuning_needs_one_context(args, world):
+    """The argument error of --tune-widths with more than one rank or more than one context
+    per rank (None otherwise): widths tuned per shard would make a shard's chains differ
+    from the same walkers' in the whole ensemble."""
+    if args.tune_widths and (world > 1 or args.gpus > 1):
+        return ("--tune-widths adapts the widths from one context's walkers: run it with one "
+                "rank and --gpus 1, then give the proposal_widths.json it writes to --widths")
+    return None
 
 
 class Shard:
@@ -347,7 +394,9 @@ def checkpoint_path(outdir, variant, rank=0, world=1):
     return outdir + ("step2_checkpoint.npz" if variant == "2" else "step2a_checkpoint.npz")
 
 
-def save_checkpoint(path, shards, out, count, config):
+def save_checkpoint(path, shards, out, count, config, widths=None):
+    """widths: the proposal widths in force where they are not the defaults (--widths,
+    --tune-widths); --resume restores them."""
     st, tr, ac, mt, ga, mm, mq = [], [], [], [], [], [], []
     nmom = 0
     for sh in shards:
@@ -361,7 +410,8 @@ def save_checkpoint(path, shards, out, count, config):
              accepts=np.concatenate(ac), mt=np.concatenate(mt), gauss=np.concatenate(ga),
              mom_n=np.int64(nmom), mom_mean=np.concatenate(mm), mom_m2=np.concatenate(mq),
              count=np.int64(count), csv_sizes=out.all_sizes(), npy_rows=np.int64(out.npy_rows),
-             config=np.array(json.dumps(config, sort_keys=True)))
+             config=np.array(json.dumps(config, sort_keys=True)),
+             **({} if widths is None else {"widths": np.asarray(widths, dtype=np.float64)}))
     os.replace(tmp, path)
 
 
@@ -390,6 +440,25 @@ def posterior_summary(shards, nsrc, group=None):
     return step3.summary_from_moments(step3.combine_moments(parts, dev), nsrc)
 
 
+def run_config(args, nsrc, variant, world):
+    """(config, widths): what a checkpoint records of the command line -- --resume refuses
+    another -- and the widths of --widths (None without).  The proposal-width flags add
+    their keys only when they are given, so a checkpoint written before they existed, or
+    without them, still resumes."""
+    config = {"image": os.path.abspath(args.image), "nsrc": nsrc, "variant": variant,
+              "walkers": args.walkers, "accept_min": args.accept_min, "burn_in": args.burn_in,
+              "iters": args.iters, "stride": args.record_stride, "exact": args.exact,
+              "fixed_bkgd": args.fixed_bkgd, "csv": not args.no_csv, "npy": args.npy,
+              "ranks": world}
+    widths = None
+    if args.widths:
+        widths = tune.load_widths(args.widths, nsrc)
+        config["widths"] = [float(v) for v in widths]
+    if args.tune_widths:
+        config["tune"] = [args.tune_widths, args.tune_every, args.tune_target, args.tune_gain]
+    return config, widths
+
+
 def main(argv=None, nsrc=2, variant="2"):
     """variant "2": apf_step2 (many walkers, {w}_finalarray_mpi.csv); "2a": the single
     walker warm-up of apf_step2a.py writing step2a.csv / step2a_acceptance_rate
@@ -402,6 +471,8 @@ def main(argv=None, nsrc=2, variant="2"):
     rank, world, local = dist.env()
     if variant != "2" or args.mpi_size > 1 or "LOCAL_RANK" not in os.environ:
         rank, world, local = 0, 1, 0
+    if tuning_needs_one_context(args, world):
+        raise SystemExit(f"error: {tuning_needs_one_context(args, world)}")
     group = dist.HostGroup(rank, world) if world > 1 else None
     say = (lambda *a: None) if (args.quiet or rank > 0) else print
     if args.mpi_rank > 0:
@@ -417,11 +488,7 @@ def main(argv=None, nsrc=2, variant="2"):
     resume = load_checkpoint(ckpt) if args.resume else None
     if args.resume and resume is None:
         raise FileNotFoundError(ckpt)
-    config = {"image": os.path.abspath(args.image), "nsrc": nsrc, "variant": variant,
-              "walkers": args.walkers, "accept_min": args.accept_min, "burn_in": args.burn_in,
-              "iters": args.iters, "stride": args.record_stride, "exact": args.exact,
-              "fixed_bkgd": args.fixed_bkgd, "csv": not args.no_csv, "npy": args.npy,
-              "ranks": world}
+    config, widths = run_config(args, nsrc, variant, world)
     if resume is not None:
         old = json.loads(str(resume["config"]))
         old.setdefault("ranks", 1)
@@ -486,6 +553,11 @@ def main(argv=None, nsrc=2, variant="2"):
     say("Found initial chi-squared:", shards[0].p_init[-1])
     say("Initial guess:", shards[0].p_init)
 
+    widths_path = outdir + "proposal_widths.json"
+    if widths is not None:
+        for sh in shards:
+            sh.s.set_widths(widths)
+
     out = Output(outdir, shards, variant, csv=not args.no_csv, npy=args.npy, base=pw0)
     count = 0
     if resume is not None:
@@ -501,6 +573,10 @@ def main(argv=None, nsrc=2, variant="2"):
                 sl = slice(sh.w0 - pw0, sh.w0 - pw0 + sh.W)
                 sh.s.set_moments(int(resume["mom_n"]), resume["mom_mean"][sl],
                                  resume["mom_m2"][sl])
+        if "widths" in resume:            # the widths in force when it was written
+            widths = np.array(resume["widths"], dtype=np.float64)
+            for sh in shards:
+                sh.s.set_widths(widths)
         out.truncate(resume["csv_sizes"], int(resume["npy_rows"]))
     else:
         # a fresh run: a checkpoint left by an earlier run in this directory must not be
@@ -511,6 +587,8 @@ def main(argv=None, nsrc=2, variant="2"):
             with open(run_id_path(outdir, variant), "w") as f:
                 f.write(run_id + "\n")
         out.start()
+        if widths is not None and rank == 0:
+            tune.save_widths(widths_path, nsrc, widths, "given")
 
     burn, stride = args.burn_in, args.record_stride
     chunk = chunk_size(shards, stride, args.chunk, args.mem_budget)
@@ -538,7 +616,7 @@ def main(argv=None, nsrc=2, variant="2"):
         with timed("waiting for the file writer"):
             bg.wait()
 
-    def commit():
+    def commit(checkpoints=True):
         # the launch's rows are folded into the device moments now (queued before the
         # next launch) and appended to the files beside the next launch (bg).
         # Checkpoints are spaced by time (and optionally by launches), not written per
@@ -552,15 +630,16 @@ def main(argv=None, nsrc=2, variant="2"):
         bg.start(lambda: out.append(lasts))
         launches += 1
         now = time.monotonic()
-        due = bool((args.checkpoint_every and launches % args.checkpoint_every == 0) or
-                   (args.checkpoint_secs > 0 and now - last_ckpt >= args.checkpoint_secs))
+        due = bool(checkpoints and
+                   ((args.checkpoint_every and launches % args.checkpoint_every == 0) or
+                    (args.checkpoint_secs > 0 and now - last_ckpt >= args.checkpoint_secs)))
         if group is not None:
             due = bool(group.broadcast(due))
         if due:
             settle()                      # the recorded file sizes
             counts = out.acceptance_counts() if count >= max(burn, 1) else None
             with timed("checkpoints"):
-                save_checkpoint(ckpt, shards, out, count, config)
+                save_checkpoint(ckpt, shards, out, count, config, widths)
             if counts is not None:        # the checkpoint's count, beside the next launch
                 bg.start(lambda: out.write_acceptance(counts))
             last_ckpt = time.monotonic()
@@ -575,6 +654,27 @@ def main(argv=None, nsrc=2, variant="2"):
         with timed("launches (sampler + chain copy)"):
             _parallel(shards, lambda sh: sh.run(n, burn, stride if record else 0, accept_min))
 
+    if args.tune_widths and count < args.tune_widths:
+        # The tuning phase, the run's first T iterations (a resumed run is past it: no
+        # checkpoint is written here, a run killed here starts again): launches of N
+        # iterations, the tuner's step queued on the device behind each.  T <= burn_in: at
+        # most the state the tuning phase ends in is recorded (count == burn_in), and every
+        # step from a recorded row to the next uses the frozen widths.
+        s0 = shards[0].s
+        s0.tune_begin(args.tune_target, args.tune_gain)
+        while count < args.tune_widths:
+            run(args.tune_every, 0 if args.iters else args.accept_min)
+            s0.tune_step()
+            count += args.tune_every
+            commit(checkpoints=False)
+            say("Loop count:", count, "(tuning the proposal widths)")
+        dT, dA, hw = s0.tune_history()
+        s0.tune_end()
+        widths = s0.get_widths()
+        tune.save_widths(widths_path, nsrc, widths, "tuned",
+                         (args.tune_target, args.tune_gain, dT, dA, hw))
+        say("Proposal widths after tuning:", widths)
+        last_ckpt = time.monotonic()
     if args.iters:
         # the files hold rows up to L = the last multiple of 10 <= iters (:355); the
         # iterations after L change no file

@@ -252,6 +252,9 @@ def main(argv=None, nsrc: int = 2):
                          "<frame>_covariance.npz")
     ap.add_argument("--covariance-thin", type=int, default=1, metavar="N",
                     help="fold every N-th row after the burn-in")
+    ap.add_argument("--widths-out", type=str, default=None, metavar="FILE",
+                    help="with --covariance: write the proposal widths the fold implies "
+                         "(covariance.proposal_widths) as a widths file for step 2's --widths")
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
     say = (lambda *a: None) if args.quiet else print
     ncor = int(np.int_(args.size))                                  # :76-77
@@ -268,6 +271,8 @@ def main(argv=None, nsrc: int = 2):
                  "terms): drop --from-moments")
     if args.covariance and args.covariance_thin < 1:
         ap.error(f"--covariance-thin {args.covariance_thin}: must be >= 1")
+    if args.widths_out and not args.covariance:
+        ap.error("--widths-out writes the widths of the --covariance fold: give --covariance")
     for flag, why in (("astrometry", "a median is not a moment"),
                       ("corner", "a histogram is not a moment"),
                       ("residuals", "moments are not samples"),
@@ -413,6 +418,11 @@ def covariance(args, chains, nsrc, stats, input_directory, say=print):
                          param_cols=range(chains.shape[2] - 1))
     for line in cv.table_lines(res):
         say(line)
+    if getattr(args, "widths_out", None):
+        # the loop's closing edge: this fold -> step 2's --widths
+        from . import tune
+        tune.save_widths(args.widths_out, nsrc, cv.proposal_widths(st, nsrc), "covariance")
+        say("Proposal widths written to", args.widths_out)
 
     def num(v):                                   # JSON has no NaN
         return float(v) if v is not None and np.isfinite(v) else None
