@@ -470,7 +470,7 @@ int olpe_corner_reset(olpe_corner *h);
  * wins; the earliest in fold order on a tie).  No result depends on the grid, the CU
  * count or the tile height; the same sequence of folds gives the same bits.  Calls on one
  * object are not thread-safe.  Not covered: the drawing, a factorised (FAST) fold, a
- * collective over the state, per-pixel chi^2 maps over all samples, photometry. */
+ * collective over the state, photometry (per-pixel chi^2 over all samples: olpe_lik below). */
 typedef struct olpe_resid olpe_resid;
 #define OLPE_RESID_PLANES 7
 /* olpe_resid_finalize's planes [OLPE_RESID_PLANES][n][n], D the data, err as apf_step2.py
@@ -521,6 +521,97 @@ int olpe_resid_reset(olpe_resid *r);
  * leaves as it is: more folds and another finalize may follow.  OLPE_ESTATE with no
  * usable sample, or when no usable sample's chi^2 is a number. */
 int olpe_resid_finalize(olpe_resid *r, double *planes, double *scalars);
+
+/* --- pointwise deviance, WAIC and DIC (apf_step2.py:106-124, :134-148) -------------------
+ * The reference's chi_squared (apf_step2.py:134-148; 3body/apf_step2_3body.py:134-148) is
+ * one number per vector and its column is only plotted; the sampler's target is
+ * exp(-chi^2 / 2) (:144-148), so a pixel's log likelihood is log p(D_i | theta) = -x_i / 2
+ * + k_i with x_i = ((D_i - M_i) / err_i)^2 and k_i = -log err_i - log(2 pi) / 2.  An
+ * olpe_lik evaluates every folded sample's build_analytical_model (:106-124; 3body
+ * :106-125) in the EXACT operation order, whatever the context's eval mode, forms t = (D -
+ * M) * (1 / err) on the staged operands and x = t * t, and keeps per pixel, about the plane
+ * c = x of a pivot vector: A1 = sum (x - c), A2 = sum (x - c)^2, and the log-sum-exp pair
+ * m = min x, L = sum exp(-(x - m) / 2) (empty: +inf, 0).  Pairs merge by m' = min(m_a, m_b),
+ * L' = L_a exp(-(m_a - m') / 2) + L_b exp(-(m_b - m') / 2), the minimum's factor exactly 1,
+ * an empty side skipped.  k_i is left out of the planes (it cancels in every comparison on
+ * the same data) and reported summed as OLPE_LIK_LOG_NORM.  Unusable rows, the best row and
+ * the pivot follow olpe_resid's rules.  A sample whose t is not finite at a pixel (a model
+ * that overflows) is not dropped at that pixel as np.ma (:134-137) would drop it: the
+ * pixel's sums become non-finite, finalize writes NaN into its planes, leaves it out of
+ * every total and counts it in OLPE_LIK_POISONED.  No result depends on the grid, the CU
+ * count or the tile height; the same sequence of folds gives the same bits.  Calls on one
+ * object are not thread-safe.  Not covered: PSIS-LOO, a factorised (FAST) fold, a
+ * collective over the state, priors (the reference has none), plots. */
+typedef struct olpe_lik olpe_lik;
+#define OLPE_LIK_PLANES 7
+/* olpe_lik_finalize's planes [OLPE_LIK_PLANES][n][n] over the ns samples folded
+ * (apf_step2.py:134-137 per pixel and sample); NaN at masked and at poisoned pixels: */
+#define OLPE_LIK_PLANE_MEAN_DEV 0 /* c + A1 / ns */
+#define OLPE_LIK_PLANE_STD_DEV 1  /* sqrt(max((A2 - A1^2 / ns) / ns, 0)): np.std of x, ddof 0 */
+#define OLPE_LIK_PLANE_LPPD 2     /* log(L / ns) - m / 2 */
+#define OLPE_LIK_PLANE_P_WAIC 3   /* (A2 - A1^2 / ns) / (ns - 1) / 4; 0 when ns = 1 */
+#define OLPE_LIK_PLANE_ELPD 4     /* [2] - [3] */
+#define OLPE_LIK_PLANE_DEV_BEST 5 /* x of the best row */
+#define OLPE_LIK_PLANE_DEV_AT 6   /* x of theta_hat; NaN without one */
+/* Its scalars; N = PIXELS - POISONED, P the number of parameters: */
+#define OLPE_LIK_SCALARS 17
+#define OLPE_LIK_USED 0           /* samples folded (usable) */
+#define OLPE_LIK_BAD 1            /* unusable rows met */
+#define OLPE_LIK_PIXELS 2         /* unmasked pixels */
+#define OLPE_LIK_POISONED 3       /* of those, pixels with a non-finite sum */
+#define OLPE_LIK_LPPD 4           /* sum of plane 2 */
+#define OLPE_LIK_P_WAIC 5         /* sum of plane 3 */
+#define OLPE_LIK_ELPD_WAIC 6      /* sum of plane 4 */
+#define OLPE_LIK_WAIC 7           /* -2 x [6] */
+#define OLPE_LIK_SE_ELPD 8        /* sqrt(N var_i(plane 4)), ddof 1 */
+#define OLPE_LIK_P_WAIC_HIGH 9    /* pixels with plane 3 > 0.4 */
+#define OLPE_LIK_MEAN_DEVIANCE 10 /* sum of plane 0 */
+#define OLPE_LIK_REDUCED 11       /* [10] / (N - P) */
+#define OLPE_LIK_DEVIANCE_BEST 12 /* sum of plane 5 */
+#define OLPE_LIK_DEVIANCE_AT 13   /* sum of plane 6: D(theta_hat) */
+#define OLPE_LIK_P_D 14           /* [10] - [13] */
+#define OLPE_LIK_DIC 15           /* [13] + 2 x [14] */
+#define OLPE_LIK_LOG_NORM 16      /* sum of k_i over the unmasked pixels */
+/* Copies ctx's staged cutout (apf_step2.py:176-210: data, 1/err, mask) device to device and
+ * takes its side, sources, bkgd_mode and device; independent of ctx afterwards.  pivot: a
+ * parameter vector (its PS - 1 parameters are read, all finite), or NULL: the first usable
+ * row folded becomes the pivot.
+ * OLPE_LIK_ROWS=4|8 picks the fold kernel's tile height (A/B; no result depends on it).
+ * OLPE_EINVAL, naming the bytes, for a frame whose partials per block exceed 1 GiB. */
+int olpe_lik_create(olpe_ctx *ctx, const double *pivot, olpe_lik **out);
+/* Frees the object of apf_step2.py:134-148's pixel terms (waits for its folds in flight). */
+void olpe_lik_destroy(olpe_lik *l);
+/* apf_step2.py:106-124 and :134-137 for rows 0, row_step, ... of walkers 0, walker_step, ...
+ * of ctx's last launch, read from its device chain in place, walker-major (async on the
+ * context's stream, no copy).  Once per launch: OLPE_ESTATE if this launch was folded
+ * already; OLPE_EINVAL for a context of another device, side, nsrc or bkgd_mode. */
+int olpe_lik_fold_ctx(olpe_lik *l, olpe_ctx *ctx, int row_step, int walker_step);
+/* apf_step2.py:106-124 and :134-137 for host rows [nsamples][PS], uploaded in bounded
+ * pieces. */
+int olpe_lik_fold_rows(olpe_lik *l, const double *rows, long long nsamples);
+/* The state (apf_step2.py:134-137 per pixel, summed over the samples): samples used,
+ * unusable rows, pivot [PS], A1, A2, m and L [n*n] each, best row [PS]; any may be NULL;
+ * pivot / best are NaN while there is none.  Waits for the folds in flight. */
+int olpe_lik_get(olpe_lik *l, long long *n, long long *n_bad, double *pivot, double *a1,
+                 double *a2, double *m, double *lsum, double *best);
+/* Merges another object's, rank's or checkpoint's state (apf_step2.py:134-137 over the
+ * union of their rows) by the rule above.  OLPE_EINVAL if the pivots' parameters differ in
+ * any bit, unless this object holds no sample yet: it then adopts the incoming pivot.  This
+ * object's rows count as folded first: the incoming best row wins only with a strictly
+ * smaller chi^2. */
+int olpe_lik_add(olpe_lik *l, long long n, long long n_bad, const double *pivot,
+                 const double *a1, const double *a2, const double *m, const double *lsum,
+                 const double *best);
+/* Empties the state (apf_step2.py:134-137 starts over); a pivot given at create stays. */
+int olpe_lik_reset(olpe_lik *l);
+/* x of one parameter vector (apf_step2.py:134-137 before the sum; PS - 1 parameters read):
+ * plane [n][n], NaN at masked pixels. */
+int olpe_lik_point(olpe_lik *l, const double *vec, double *plane);
+/* The planes and scalars above (apf_step2.py:134-148 per pixel) from the state, which it
+ * leaves as it is.  theta_hat: the vector of DIC's D(theta_hat) (step 3 passes the column
+ * means), or NULL: plane 6 and scalars 13 - 15 are NaN.  OLPE_ESTATE with no usable sample,
+ * or when no usable sample's chi^2 is a number. */
+int olpe_lik_finalize(olpe_lik *l, const double *theta_hat, double *planes, double *scalars);
 
 /* --- autocorrelation times of the chains (apf_step3.py:582-601) --------------------------
  * The reference draws every walker's trace of every parameter (apf_step3.py:582-601) and

@@ -117,6 +117,15 @@ SIGNATURES = {
     "olpe_resid_add": (_i, [_P, _ll, _ll, _pd, _pd, _pd, _pd]),
     "olpe_resid_reset": (_i, [_P]),
     "olpe_resid_finalize": (_i, [_P, _pd, _pd]),
+    "olpe_lik_create": (_i, [_P, _pd, C.POINTER(_P)]),
+    "olpe_lik_destroy": (None, [_P]),
+    "olpe_lik_fold_ctx": (_i, [_P, _P, _i, _i]),
+    "olpe_lik_fold_rows": (_i, [_P, _pd, _ll]),
+    "olpe_lik_get": (_i, [_P, _pll, _pll, _pd, _pd, _pd, _pd, _pd, _pd]),
+    "olpe_lik_add": (_i, [_P, _ll, _ll, _pd, _pd, _pd, _pd, _pd, _pd]),
+    "olpe_lik_reset": (_i, [_P]),
+    "olpe_lik_point": (_i, [_P, _pd, _pd]),
+    "olpe_lik_finalize": (_i, [_P, _pd, _pd, _pd]),
     "olpe_acf_create": (_i, [_i, _i, _i, C.POINTER(_P)]),
     "olpe_acf_destroy": (None, [_P]),
     "olpe_acf_fold_ctx": (_i, [_P, _P]),

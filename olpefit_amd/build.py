@@ -15,10 +15,11 @@ SOURCES = [os.path.join(CSRC, f) for f in ("olpe.hip", "olpe_comm.hip", "olpe_mo
                                             "olpe_astrom.hip", "olpe_csv.cpp",
                                             "olpe_corner.hip", "olpe_resid.hip",
                                             "olpe_acf.hip", "olpe_phot.hip", "olpe_cov.hip",
-                                            "olpe_tune.hip")]
+                                            "olpe_tune.hip", "olpe_lik.hip")]
 DEPS = SOURCES + [os.path.join(CSRC, f) for f in ("olpe_device.h", "olpe_internal.h",
                                                  "olpe_fold.h", "olpe_select.h", "olpe_reduce.h",
-                                                 "olpe_store.h", "exp_table.h",
+                                                 "olpe_store.h", "olpe_samples.h",
+                                                 "exp_table.h",
                                                  "olpe_comm_proto.h")] + [
     os.path.join(REPO, "include", h) for h in ("olpe.h", "olpe_test.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -97,6 +97,7 @@ class Sampler:
         self._mask = np.ascontiguousarray(mask, dtype=np.uint8)
         self.n = img.shape[1]
         self.nsrc = nsrc
+        self.bkgd_mode = bkgd_mode
         self.np_ = param_count(nsrc)
         self.ps = self.np_ + 1
         self.W = 0

@@ -1,5 +1,5 @@
 // olpe_fold.h -- what the step-3 fold objects (olpe_astrom, olpe_corner, olpe_resid,
-// olpe_acf, olpe_phot, olpe_cov) share on the host: the device, a stream and an event of
+// olpe_acf, olpe_phot, olpe_cov, olpe_lik) share on the host: the device, a stream and an event of
 // their own, device buffers, and the one statement of how a fold joins a sampler's stream
 // (fold_run).  No device code.
 //

@@ -10,7 +10,7 @@ state is three images and a few numbers; it merges by addition (``add``) wheneve
 pivots are equal, so ranks, contexts and checkpoints combine on the host.
 
 Not covered: the drawing, a factorised (FAST) fold, a collective over the state,
-per-pixel chi^2 maps over all samples, photometry.  Nothing here imports matplotlib or
+photometry (per-pixel chi^2 over all samples: ``predictive.Predictive``).  Nothing here imports matplotlib or
 the oracle.
 """
 from __future__ import annotations

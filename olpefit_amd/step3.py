@@ -186,7 +186,8 @@ def main(argv=None, nsrc: int = 2):
     chains' integrated autocorrelation times and effective sample sizes (``autocorr``),
     ``--photometry`` the flux ratio, delta magnitude, FWHM and S/N (``photometry``),
     ``--covariance`` the parameter covariance, the companions' error ellipses, the conditional
-    widths and the multivariate Gelman-Rubin statistic (``covariance``)."""
+    widths and the multivariate Gelman-Rubin statistic (``covariance``), ``--waic`` every
+    pixel's posterior deviance, WAIC and DIC (``waic``)."""
     import argparse
     import json
     import sys
@@ -231,6 +232,16 @@ def main(argv=None, nsrc: int = 2):
     ap.add_argument("--bkgd-mode", type=int, choices=(0, 1), default=0,
                     help="the background parameter of the models --residuals evaluates: 0 as "
                          "step 2's default, 1 as its --fixed-bkgd")
+    ap.add_argument("--waic", action="store_true",
+                    help="posterior mean / scatter of every pixel's deviance, WAIC and DIC of "
+                         "the chains (GPU); writes <frame>_waic.npz and three FITS files")
+    ap.add_argument("--waic-thin", type=int, default=1, metavar="N",
+                    help="fold every N-th row after the burn-in (a full fold costs more "
+                         "than sampling the rows did)")
+    ap.add_argument("--waic-against", type=str, default=None, metavar="FILE",
+                    help="with --waic: compare pixel by pixel with another run's "
+                         "<frame>_waic.npz of the same cutout (2 against 3 sources, "
+                         "--bkgd-mode 0 against 1)")
     ap.add_argument("--autocorr", action="store_true",
                     help="integrated autocorrelation time and effective sample size per "
                          "parameter of the chains (GPU); writes <frame>_autocorr.npz")
@@ -276,6 +287,7 @@ def main(argv=None, nsrc: int = 2):
     for flag, why in (("astrometry", "a median is not a moment"),
                       ("corner", "a histogram is not a moment"),
                       ("residuals", "moments are not samples"),
+                      ("waic", "moments are not samples"),
                       ("autocorr", "moments hold no order"),
                       ("photometry", "a percentile is not a moment")):
         if args.from_moments and getattr(args, flag):
@@ -285,6 +297,10 @@ def main(argv=None, nsrc: int = 2):
         ap.error(f"--autocorr-max-lag {args.autocorr_max_lag}: a multiple of 64 from 64 to 1024")
     if args.residuals_thin < 1:
         ap.error(f"--residuals-thin {args.residuals_thin}: must be >= 1")
+    if args.waic_thin < 1:
+        ap.error(f"--waic-thin {args.waic_thin}: must be >= 1")
+    if args.waic_against and not args.waic:
+        ap.error("--waic-against compares the --waic fold: give --waic")
     if args.photometry_thin < 1:
         ap.error(f"--photometry-thin {args.photometry_thin}: must be >= 1")
     if args.from_moments:
@@ -346,6 +362,8 @@ def main(argv=None, nsrc: int = 2):
         out["photometry"] = phot
     if args.covariance:
         out["covariance"] = covariance(args, chains, nsrc, stats, input_directory, say)
+    if args.waic:
+        out["waic"] = waic(args, chains, nsrc, stats, input_directory, say)
     with open(input_directory + "step3_summary.json", "w") as f:
         json.dump(out, f, indent=1)
     return out
@@ -497,6 +515,48 @@ def residuals(args, chains, nsrc, input_directory, say=print):
         say(f"{k:>18} {v:.10g}")
     return {"file": prefix + "_residuals.npz", "fits": files, "thin": args.residuals_thin,
             "bkgd_mode": args.bkgd_mode, **scal}
+
+
+def waic(args, chains, nsrc, stats, input_directory, say=print):
+    """What the reference's chi^2 column (apf_step2.py:134-148; 3body :134-148), which is
+    only plotted, cannot say: how well the model predicts every pixel over the chains
+    [N, M, PS] already read, and which of two runs predicts the image better.  Every
+    ``--waic-thin``-th row's ``build_analytical_model`` (apf_step2.py:106-124; 3body
+    :106-125) is evaluated on the GPU (predictive.Predictive) on the frame as step 2 staged
+    it (apf_step2.py:160-161, :176-210; ``--bkgd-mode`` as ``--residuals``) and its
+    per-pixel deviance folded; theta_hat of DIC is the column means just computed.  Writes
+    ``<frame>_waic.npz`` and ``<frame>_meandev.fits``, ``_elpd.fits``, ``_pwaic.fits``
+    beside the chain files and returns what ``step3_summary.json`` records.
+    ``--waic-against`` adds ``predictive.compare`` of this run against another's npz."""
+    from . import fitsio, predictive as pr
+    from .core import Sampler
+    labels = NAMES_2 if nsrc == 2 else NAMES_3
+    image, hdr = fitsio.getdata_header(args.image)
+    say('Folding pointwise deviance (WAIC, DIC)...')
+    prefix = results_prefix(args, input_directory)
+    theta_hat = np.array([stats[k]["mean"] for k in labels[:-1]])
+    if not np.isfinite(theta_hat).all():
+        raise ValueError("a column mean is not finite: --waic needs an additional_burnin "
+                         "that drops the NaN seed row")
+    with Sampler(image, hdr["ITIME"], hdr["COADDS"], hdr["MULTISAM"], hdr["SAMPMODE"],
+                 nsrc=nsrc, bkgd_mode=args.bkgd_mode) as s, pr.Predictive(s) as p:
+        p.fold_rows(chains[::args.waic_thin])
+        _, scal = p.save(prefix + "_waic.npz", theta_hat=theta_hat, thin=args.waic_thin)
+        files = p.write_fits(prefix, theta_hat=theta_hat)
+    cmp_ = None
+    if args.waic_against:
+        cmp_ = pr.compare(prefix + "_waic.npz", args.waic_against)
+        cmp_["file"] = args.waic_against
+    for line in pr.table_lines(scal, cmp_):
+        say(line)
+
+    def num(v):                                   # JSON has no NaN
+        return v if isinstance(v, int) else (float(v) if np.isfinite(v) else None)
+    out = {"file": prefix + "_waic.npz", "fits": files, "thin": args.waic_thin,
+           "bkgd_mode": args.bkgd_mode, **{k: num(v) for k, v in scal.items()}}
+    if cmp_ is not None:
+        out["against"] = {k: (v if isinstance(v, str) else num(v)) for k, v in cmp_.items()}
+    return out
 
 
 def resolve_prepost(args):
