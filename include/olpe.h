@@ -88,6 +88,19 @@ int olpe_model(olpe_ctx *ctx, const double *params, double *model_out);
 /* chi_squared(image_nanmask, build_analytical_model(p), err) (apf_step2.py:314-316,
  * :134-137) for W parameter vectors [W][PS] -> chi2_out[W]. */
 int olpe_chi2_batch(olpe_ctx *ctx, const double *params, int W, double *chi2_out);
+/* Gauss-Newton sums of explicit parameter vectors (no reference line: the reference
+ * has no optimiser; model of apf_step2.py:106-124, residual of :134-137).  With
+ * r_p = (D_p - M_p) / err_p and J_pk = (dM_p / dtheta_k) / err_p over the usable pixels of
+ * the cutout (masked pixels contribute exact zeros):  chi2 = sum r^2,  grad[k] = sum J_pk r_p
+ * (so d chi^2 / d theta_k = -2 grad[k]),  jtj[k][l] = sum J_pk J_pl.  The model is the EXACT
+ * one whatever the context's eval mode.  In bkgd_mode 0 of the 2-source layout p[12] is
+ * sigma_x of the wide set and the background: its column is the sum of both.  A vector's
+ * outputs are the same bits for any W, any place in the batch and every repeat.  A vector
+ * with a non-finite parameter, or whose model is not finite at a usable pixel, gets NaN in
+ * all its outputs; the rest of the batch is untouched.  Waits for the result. */
+int olpe_normal_batch(olpe_ctx *ctx, const double *params /*[W][PS]*/, int W,
+                      double *chi2 /*[W]*/, double *grad /*[W][P]*/,
+                      double *jtj /*[W][P][P], symmetric, both halves written*/);
 
 /* --- walker ensemble (device resident) ------------------------------------------ */
 /* np.random.seed(seeds[w]) for W walkers (init_genrand semantics)

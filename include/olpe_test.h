@@ -38,6 +38,12 @@ int olpe_test_hold_handoff(olpe_ctx *ctx, int on);
  * untouched.  nrec may be 0.  OLPE_ESTATE before olpe_seed. */
 int olpe_test_chain_set(olpe_ctx *ctx, const double *chain, long long nrec);
 
+/* The derivatives dM_p / dtheta_k of the model at the PS-vector vec, without the 1 / err
+ * weight and at every pixel, masked or not: planes[P][n][n], through the device expressions
+ * of olpe_normal_batch (olpe_normal.hip, pixel_jac), so that a wrong lane-to-pixel map or
+ * chain-rule entry of the sums can be told apart per pixel. */
+int olpe_test_jacobian(olpe_ctx *ctx, const double *vec, double *planes);
+
 #ifdef __cplusplus
 }
 #endif

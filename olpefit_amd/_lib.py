@@ -48,6 +48,7 @@ SIGNATURES = {
     "olpe_set_eval_mode": (_i, [_P, _i]),
     "olpe_model": (_i, [_P, _pd, _pd]),
     "olpe_chi2_batch": (_i, [_P, _pd, _i, _pd]),
+    "olpe_normal_batch": (_i, [_P, _pd, _i, _pd, _pd, _pd]),
     "olpe_seed": (_i, [_P, _pu32, _i]),
     "olpe_state_set": (_i, [_P, _pd, _pd, _pd]),
     "olpe_state_get": (_i, [_P, _pd, _pd, _pd]),
@@ -155,6 +156,7 @@ SIGNATURES = {
     "olpe_moments_fault": (_i, [_P, _i]),
     "olpe_test_hold_handoff": (_i, [_P, _i]),
     "olpe_test_chain_set": (_i, [_P, _pd, _ll]),
+    "olpe_test_jacobian": (_i, [_P, _pd, _pd]),
 }
 
 _lib = None

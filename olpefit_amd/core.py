@@ -159,6 +159,27 @@ class Sampler:
         check(self._lib.olpe_chi2_batch(self._ctx, _dptr(p), p.shape[0], _dptr(out)))
         return float(out[0]) if single else out
 
+    def normal_equations(self, vecs):
+        """The Gauss-Newton sums (olpe_normal_batch) of one vector [P] / [PS] or a batch
+        [W, P] / [W, PS]: (chi2 [W], grad [W, P], jtj [W, P, P]) with r = (D - M) / err and
+        J = (dM / dtheta) / err over the usable pixels, chi2 = sum r^2, grad = J^T r (the
+        gradient of chi^2 is -2 grad), jtj = J^T J.  The EXACT model whatever the eval mode;
+        a vector that is not finite, or whose model is not, gets NaN throughout."""
+        p = self._vec(vecs).reshape(-1, self.ps)
+        W, P = p.shape[0], self.np_
+        chi2, grad, jtj = np.empty(W), np.empty((W, P)), np.empty((W, P, P))
+        check(self._lib.olpe_normal_batch(self._ctx, _dptr(p), W, _dptr(chi2), _dptr(grad),
+                                          _dptr(jtj)))
+        return chi2, grad, jtj
+
+    def test_jacobian(self, vec):
+        """Test hook (olpe_test_jacobian, include/olpe_test.h): dM / dtheta_k per pixel,
+        unweighted, [P, n, n], through the device expressions of ``normal_equations``."""
+        p = self._vec(vec).reshape(self.ps)
+        out = np.empty((self.np_, self.n, self.n))
+        check(self._lib.olpe_test_jacobian(self._ctx, _dptr(p), _dptr(out)))
+        return out
+
     # -- ensemble ---------------------------------------------------------------
     def seed(self, seeds):
         """np.random.seed(seeds[w]) for each walker w; allocates the ensemble."""

@@ -28,7 +28,10 @@ length instead of accept_min), ``--record-stride``, ``--gpus``, ``--exact``,
 ``--fixed-bkgd``, ``--chunk``, ``--mem-budget``, ``--checkpoint-secs``,
 ``--checkpoint-every``, ``--resume``, ``--no-csv``, ``--npy``, and the proposal widths'
 ``--widths`` and ``--tune-widths`` (with ``--tune-every``, ``--tune-target``,
-``--tune-gain``), which write ``proposal_widths.json`` beside the chain files.
+``--tune-gain``), which write ``proposal_widths.json`` beside the chain files, and
+``-i map`` (both layouts) with ``--start-scatter``: the walkers start at the best fit
+``apf_map.py`` left in ``map_fit.json``, or each at its own draw from the fit's Laplace
+approximation (olpefit_amd.mapfit).
 """
 from __future__ import annotations
 
@@ -42,7 +45,7 @@ import time
 
 import numpy as np
 
-from . import _lib, dist, fitsio, pipeline, step3, tune
+from . import _lib, dist, fitsio, mapfit, pipeline, step3, tune
 from .core import Sampler
 
 MAX_CHUNK = 20000          # iterations per launch when memory allows
@@ -79,7 +82,16 @@ def parse(argv, nsrc, variant="2"):
         ap.set_defaults(walkers=1, iters=5000, burn_in=0, accept_min=0, initial_guess_option="1")
     if nsrc == 2 and variant == "2":
         ap.add_argument("-i", "--initial_guess_option", type=str,
-                        help="-i 1 for the step 1 guess, -i 2a for the step 2a output")
+                        help="-i 1 for the step 1 guess, -i 2a for the step 2a output, -i map "
+                             "for the best fit apf_map.py left in map_fit.json")
+    if nsrc == 3 and variant == "2":
+        ap.add_argument("-i", "--initial_guess_option", type=str, choices=["map"],
+                        help="-i map for the best fit apf_map_3body.py left in map_fit.json")
+    if variant == "2":
+        ap.add_argument("--start-scatter", type=float, default=None, metavar="S",
+                        help="with -i map: walker w starts at its own draw from the fit's "
+                             "Laplace approximation, inflated by S (mapfit.laplace_draws), "
+                             "instead of every walker at the best fit")
     ap.add_argument("--walkers", type=int, default=None if variant == "2" else 1,
                     help="independent walkers (the reference's MPI processes; default: the "
                          "size of an mpiexec launch, else 24)")
@@ -142,6 +154,12 @@ def parse(argv, nsrc, variant="2"):
         ap.error("apf_step2a runs one walker (it writes a single step2a.csv)")
     if args.walkers < 1 or args.record_stride < 1 or args.chunk < 0:
         ap.error("--walkers and --record-stride must be >= 1, --chunk >= 0")
+    scatter = getattr(args, "start_scatter", None)
+    if scatter is not None:
+        if getattr(args, "initial_guess_option", None) != "map":
+            ap.error("--start-scatter draws from the fit of -i map")
+        if not (np.isfinite(scatter) and scatter > 0.0):
+            ap.error("--start-scatter must be finite and > 0")
     T, N = args.tune_widths, args.tune_every
     if T < 0:
         ap.error("--tune-widths must be >= 0")
@@ -180,7 +198,9 @@ def tuning_needs_one_context(args, world):
 class Shard:
     """The walkers [w0, w0 + W) on one GPU."""
 
-    def __init__(self, img, hdr, nsrc, device, w0, W, p0, seeds, exact, bkgd_mode):
+    def __init__(self, img, hdr, nsrc, device, w0, W, p0, seeds, exact, bkgd_mode,
+                 starts=None):
+        # starts: every walker's own first parameters [walkers, P] (--start-scatter)
         self.s = Sampler(img, hdr["ITIME"], hdr["COADDS"], hdr["MULTISAM"], hdr["SAMPMODE"],
                          nsrc=nsrc, bkgd_mode=bkgd_mode, device=device)
         self.s.set_eval_mode("exact" if exact else "fast")
@@ -191,7 +211,12 @@ class Shard:
             p[-1] = self.s.chi_squared(p)                       # apf_step2.py:283-289
         self.p_init = p
         self.s.seed(seeds[w0:w0 + W])
-        self.s.set_state(np.tile(p, (W, 1)))
+        state = np.tile(p, (W, 1))
+        if starts is not None:
+            state[:, :-1] = starts[w0:w0 + W]
+            with np.errstate(all="ignore"):
+                state[:, -1] = self.s.chi_squared(state)
+        self.s.set_state(state)
         self.last = None                 # the last launch's chain [W, nrec, PS]
 
     def snapshot(self):
@@ -456,6 +481,10 @@ def run_config(args, nsrc, variant, world):
         config["widths"] = [float(v) for v in widths]
     if args.tune_widths:
         config["tune"] = [args.tune_widths, args.tune_every, args.tune_target, args.tune_gain]
+    if getattr(args, "initial_guess_option", None) == "map":
+        config["init"] = "map"
+        if args.start_scatter is not None:
+            config["start_scatter"] = float(args.start_scatter)
     return config, widths
 
 
@@ -489,6 +518,12 @@ def main(argv=None, nsrc=2, variant="2"):
     if args.resume and resume is None:
         raise FileNotFoundError(ckpt)
     config, widths = run_config(args, nsrc, variant, world)
+    bkgd_mode = 1 if args.fixed_bkgd else 0
+    fit = None
+    if config.get("init") == "map":
+        # the best fit and its Laplace approximation (apf_map.py); refused when it was made
+        # for another layout, background mode or cutout side
+        fit = mapfit.load_map(outdir + "map_fit.json", nsrc, bkgd_mode, int(image.shape[1]))
     if resume is not None:
         old = json.loads(str(resume["config"]))
         old.setdefault("ranks", 1)
@@ -505,9 +540,15 @@ def main(argv=None, nsrc=2, variant="2"):
             diff = {k: (old.get(k), config.get(k)) for k in set(old) | set(config)
                     if old.get(k) != config.get(k)}
             raise ValueError(f"--resume: the checkpoint was written with other settings {diff}")
+        if fit is not None and not np.array_equal(p0[:-1], fit["theta_hat"]):
+            raise ValueError(f"--resume: {outdir}map_fit.json holds another best fit than the "
+                             "one this run started from")
         say(f"Resuming from {ckpt} at count {int(resume['count'])}")
     else:
-        if getattr(args, "initial_guess_option", None) == "2a":  # :248-256
+        if fit is not None:
+            say("I am taking the initial guess from the best fit (map_fit.json)")
+            p0 = np.append(fit["theta_hat"], 0.0)
+        elif getattr(args, "initial_guess_option", None) == "2a":  # :248-256
             say("I am taking the initial guess from Step 2a output")
             p0 = pipeline.read_step2a(outdir + "step2a.csv")
         else:
@@ -548,8 +589,15 @@ def main(argv=None, nsrc=2, variant="2"):
         # every rank, whatever its shard size)
         dev0 = args.device + local * args.gpus
     bounds = [pw0 + (g * pW) // ng for g in range(ng + 1)]
+    starts = None
+    if fit is not None and args.start_scatter is not None:
+        # a stream per walker, keyed by its seed: a shard's walkers start where the whole
+        # ensemble's do
+        starts = np.zeros((W, len(p0) - 1))
+        starts[pw0:pw0 + pW] = mapfit.laplace_draws(fit, seeds[pw0:pw0 + pW], args.start_scatter)
+        say(f"walkers start at draws from the Laplace approximation x {args.start_scatter}")
     shards = [Shard(image, hdr, nsrc, dev0 + g, bounds[g], bounds[g + 1] - bounds[g], p0,
-                    seeds, args.exact, 1 if args.fixed_bkgd else 0) for g in range(ng)]
+                    seeds, args.exact, bkgd_mode, starts) for g in range(ng)]
     say("Found initial chi-squared:", shards[0].p_init[-1])
     say("Initial guess:", shards[0].p_init)
 

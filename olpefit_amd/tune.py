@@ -11,7 +11,7 @@ rates between launches (``tune_begin`` / ``tune_step``; include/olpe.h states th
 The widths file is JSON::
 
     {"format": "olpefit-widths-1", "nsrc": 2, "names": [...P names...],
-     "widths": [...P values...], "source": "given" | "tuned" | "covariance",
+     "widths": [...P values...], "source": "given" | "tuned" | "covariance" | "laplace",
      "history": {"target", "gain", "dT" [k][P], "dA" [k][P], "widths" [k][P]}}   (tuned only)
 
 Values are written with ``repr`` precision (``json`` does), so a file round-trips bit for
@@ -27,7 +27,7 @@ import numpy as np
 from .step3 import NAMES_2, NAMES_3
 
 FORMAT = "olpefit-widths-1"
-SOURCES = ("given", "tuned", "covariance")
+SOURCES = ("given", "tuned", "covariance", "laplace")
 
 #: apf_step2.py:234 and 3body/apf_step2_3body.py:220-238 (the device's own copy is
 #: olpe.hip's c_widths2 / c_widths3; tests/test_widths_cpu.py compares the two texts)
