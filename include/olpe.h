@@ -154,12 +154,25 @@ int olpe_rng_stream(olpe_ctx *ctx, int kind, int n, void *out);
 int olpe_trace_enable(olpe_ctx *ctx, int on);
 int olpe_trace_read(olpe_ctx *ctx, double *out);
 
-/* Wait for the context's stream. */
+/* Launch overlap.  Consecutive olpe_run launches of one context run on two sampler
+ * streams, alternately, and a launch may start while its predecessor's last walkers still
+ * run: each of its walkers then waits, on the device, for that walker's end in the
+ * predecessor.  This happens when both launches run the sampler's unit queue over the same
+ * walkers, nothing but olpe_moments_accumulate was called on the context between them, no
+ * trace is recorded, and the environment variable OLPE_OVERLAP is not 0; otherwise a launch
+ * waits for its predecessor's end.  olpe_moments_accumulate follows the launch it folds and
+ * the fold before it.  Every other call that touches the device runs behind all launches
+ * and folds enqueued so far, and the next launch behind it: results and their order are
+ * those of one stream.  A process with one context opens three hardware queues. */
+
+/* Wait for everything the context has enqueued. */
 int olpe_sync(olpe_ctx *ctx);
-/* Duration (ms, HIP events on the launch stream) of the last sampler launch. */
+/* Duration (ms, HIP events on the launch's stream) of the last sampler launch. */
 int olpe_last_kernel_ms(olpe_ctx *ctx, double *ms);
 /* Durations of the last n sampler launches (oldest first; n <= 64 and <= launches so
- * far): launches can be queued back to back and timed afterwards. */
+ * far): launches can be queued back to back and timed afterwards.  A launch's time runs to
+ * its end from its start or, where it overlapped its predecessor, from that launch's end
+ * if that is later: back-to-back launches then sum to the time they took together. */
 int olpe_kernel_times(olpe_ctx *ctx, int n, double *ms_out);
 /* Chunks per walker of the last sampler launch (1 = whole walkers; > 1 when the launch
  * cut each walker's iterations into chunks to fill the resident waves).

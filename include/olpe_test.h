@@ -31,6 +31,11 @@ int olpe_moments_fault(olpe_ctx *ctx, int where);
  * not all be resident (too many walkers for the device). */
 int olpe_test_hold_handoff(olpe_ctx *ctx, int on);
 
+/* How many of the context's sampler launches so far overlapped their predecessor (olpe.h,
+ * "Launch overlap"): started behind the launch before it, its chunk 0 waiting per walker
+ * on the predecessor's last hand-off tag, instead of behind the predecessor's end. */
+int olpe_test_overlaps(olpe_ctx *ctx, long long *count);
+
 /* Upload chain[W][nrec][PS] into the context's device chain buffer as if a sampler launch
  * had just recorded it: grows the buffer as olpe_run does, sets the launch's row count,
  * counts one launch (so olpe_moments_accumulate and every *_fold_ctx accept it), records

@@ -155,6 +155,7 @@ SIGNATURES = {
     "olpe_cov_reset": (_i, [_P]),
     "olpe_moments_fault": (_i, [_P, _i]),
     "olpe_test_hold_handoff": (_i, [_P, _i]),
+    "olpe_test_overlaps": (_i, [_P, _pll]),
     "olpe_test_chain_set": (_i, [_P, _pd, _ll]),
     "olpe_test_jacobian": (_i, [_P, _pd, _pd]),
 }

@@ -406,6 +406,13 @@ class Sampler:
         wait happens by construction (olpe_unit_stats counts it)."""
         check(self._lib.olpe_test_hold_handoff(self._ctx, 1 if on else 0))
 
+    def overlaps(self) -> int:
+        """Test hook (olpe_test_overlaps, include/olpe_test.h): sampler launches so far
+        that overlapped their predecessor."""
+        n = C.c_longlong(0)
+        check(self._lib.olpe_test_overlaps(self._ctx, C.byref(n)))
+        return int(n.value)
+
     def test_chain_set(self, chain):
         """Test hook (olpe_test_chain_set, include/olpe_test.h): chain [W, nrec, PS]
         becomes the device chain as if a sampler launch had just recorded it (one launch

@@ -100,6 +100,11 @@ struct GibbsArgs {
   int units;
   unsigned *uflag;     // [W]
   unsigned utag;       // this launch's tag base (a multiple of 16)
+  // a launch that overlaps its predecessor (olpe_run): chunk 0 of walker w waits until
+  // uflag[w] == ptag, the tag the walker's last chunk of that launch publishes (the last
+  // chunk of a queue launch always publishes utag + units); 0 = none, today's path
+  unsigned ptag;
+  unsigned long long *ustats;   // hand-off statistics: waits, their 100 MHz ticks
   unsigned *uerr;      // set to 1 when a hand-off wait times out (olpe_sync reports it)
   unsigned long long wait_ticks;   // a hand-off wait gives up after this many 100 MHz ticks
   int balance;         // progress balancing of the LDS sampler (launch_gibbs_t picks)
@@ -306,6 +311,24 @@ __device__ __forceinline__ void hold_handoff(unsigned *hold, unsigned *err, unsi
   }
 }
 
+// The gate in front of a launch that overlaps its predecessor (launch_gibbs_t): one wave
+// that ends once the predecessor's queue counter has left its base, that is once a wave
+// of the predecessor has taken a unit and so is resident.  Bounded like unit_wait.
+__global__ __launch_bounds__(64) void olpe_overlap_gate_kernel(unsigned long long *queue,
+                                                               unsigned long long base,
+                                                               unsigned *err,
+                                                               unsigned long long limit) {
+  if (threadIdx.x != 0) return;
+  const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+  while (__hip_atomic_load((gu64 *)queue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= base) {
+    if (__builtin_amdgcn_s_memrealtime() - t0 > limit) {
+      __hip_atomic_store((gu32 *)err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      break;
+    }
+    __builtin_amdgcn_s_sleep(16);
+  }
+}
+
 // wave priority of the step's control chain (the sweep runs at 0, or 0/1 with balancing)
 constexpr int kCtrlPrio = 2;
 // the global-memory sampler's minimum waves per SIMD (its launch bound, below)
@@ -440,9 +463,14 @@ void olpe_gibbs_kernel(GibbsArgs A) {
       it_e = q * (k + 1) + (r * (k + 1)) / units;
       // the walker's previous chunk ran on another wave: wait for its hand-off
       if (k > 0 && active)
-        unit_wait(K()->uflag + w, K()->utag + (unsigned)k, K()->uerr, K()->queue + 2, lane,
+        unit_wait(K()->uflag + w, K()->utag + (unsigned)k, K()->uerr, K()->ustats, lane,
                   K()->wait_ticks, K()->hold);
     }
+    // an overlapped launch: the walker's last chunk of the previous launch may still be
+    // running on a wave of that launch -- the same wait, then the same one acquire
+    if (k == 0 && K()->ptag && active)
+      unit_wait(K()->uflag + w, K()->ptag, K()->uerr, K()->ustats, lane, K()->wait_ticks,
+                K()->hold);
     // ring sampler: the batch's waves run max(it_e - it_s) lockstep steps; a wave past
     // its own iterations (or without a unit) keeps the phase barriers (idle steps)
     int it_end = it_e;
@@ -789,9 +817,11 @@ void olpe_gibbs_kernel(GibbsArgs A) {
       st_wt(K()->gauss + w, mt.gauss);
       st_wt(K()->done_at + w, done_at);
     }
-    // hand the walker to the wave that takes its next chunk
-    if (k < K()->units - 1) {
-      if (k == 0 && K()->hold) hold_handoff(K()->hold, K()->uerr, K()->wait_ticks);
+    // hand the walker to the wave that takes its next chunk; the last chunk hands it to
+    // the next launch, which may already be running (ptag)
+    if (K()->queue) {
+      if (k == 0 && k < K()->units - 1 && K()->hold)
+        hold_handoff(K()->hold, K()->uerr, K()->wait_ticks);
       unit_publish(K()->uflag + w, K()->utag + (unsigned)(k + 1), lane);
     }
     wave_sync();      // the slice is reused by the wave's next walker
@@ -990,8 +1020,15 @@ size_t lds_bytes(const olpe_ctx *c, int wpb, bool ring = false) {
 }
 
 
+// what olpe_run hands a launch: its slot in the event ring, and whether main-class work
+// was enqueued since the previous launch (then the launch follows it and overlaps nothing)
+struct LaunchSlot {
+  int slot;
+  bool serial;
+};
+
 template <int NSRC, int NT, bool LDS, int WPB, bool FAST>
-int launch_gibbs_t(olpe_ctx *c, const GibbsArgs &a) {
+int launch_gibbs_t(olpe_ctx *c, const GibbsArgs &a, const LaunchSlot &l) {
   constexpr bool RING = !LDS && FAST && ring_wpb(NT, WPB);    // (olpe_gibbs_kernel)
   const size_t shm = lds_bytes(c, WPB, RING);
   auto k = olpe_gibbs_kernel<NSRC, NT, LDS, WPB, FAST>;
@@ -1005,12 +1042,16 @@ int launch_gibbs_t(olpe_ctx *c, const GibbsArgs &a) {
     attr_set.fetch_or(bit, std::memory_order_release);
   }
   unsigned blocks = (unsigned)((a.W + WPB - 1) / WPB);
+  const int p = c->par;                       // this launch's parity (olpe_run)
+  const hipStream_t s = c->sstream[p];
   GibbsArgs q = a;
   q.queue = nullptr;
   q.qbase = 0;
   q.units = 1;
   q.uflag = c->d_uflag;
   q.utag = 0;
+  q.ptag = 0;
+  q.ustats = c->d_queue + 2;
   q.uerr = reinterpret_cast<unsigned *>(c->d_queue + 1);
   q.stagger = c->stagger;
   q.hold = nullptr;
@@ -1030,8 +1071,8 @@ int launch_gibbs_t(olpe_ctx *c, const GibbsArgs &a) {
     // persistent grid: as many workgroups as fit on the device at once, the work
     // units handed out by the queue
     if (blocks > resident) blocks = resident;
-    q.queue = c->d_queue;
-    q.qbase = c->qbase;
+    q.queue = c->d_queue + (p ? 5 : 0);
+    q.qbase = c->qbase2[p];
     q.units = units;
     c->utag += 16;
     q.utag = c->utag;
@@ -1044,10 +1085,38 @@ int launch_gibbs_t(olpe_ctx *c, const GibbsArgs &a) {
         return set_err(OLPE_EINVAL, "olpe_test_hold_handoff: %lld walkers need %u resident "
                        "workgroups, the device holds %u", a.W, need, resident);
       blocks = need;
-      HIPCHK(hipMemsetAsync(c->d_queue + 4, 0, sizeof(unsigned long long), c->stream));
-      q.hold = reinterpret_cast<unsigned *>(c->d_queue + 4);
+      q.hold = reinterpret_cast<unsigned *>(c->d_queue + (p ? 6 : 4));
     }
   }
+  // Does this launch overlap its predecessor?  (olpe_run has put this
+  // stream behind any main-class work already.)  Both run the unit queue over the same
+  // walkers, nothing main-class lies between them, no trace is written (its buffer is one
+  // per context), and OLPE_OVERLAP is not 0: then chunk 0 of every walker waits for the
+  // tag its last chunk of the predecessor publishes.  Otherwise the launch waits for the
+  // predecessor's end event and takes today's path.
+  //
+  // Why an overlapped launch cannot deadlock although its waves hold slots while they
+  // wait: launch k+1 sits on the stream of launch k-1, so it cannot dispatch before k-1
+  // has completed; launch k has been dispatchable since k-2 completed and takes slots as
+  // k-1's tail frees them, so k has resident waves before k+1 has any; resident waves of
+  // k keep drawing units until k's queue is empty; so every unit a wave of k+1 can wait
+  // for is taken by a resident wave of k, which finishes it whatever k+1 does.  (And the
+  // wait is bounded in real time like every hand-off's: wait_ticks, the error word.)
+  // The second step holds only while launches follow each other closely.  Where k-1 was
+  // long done when k and k+1 were enqueued (the first pair after a main-class call, a
+  // slow host), the two dispatch in whatever order their queues are served: k+1 with a
+  // grid that fills the device would then wait on a launch that cannot place a workgroup,
+  // until the polls time out.  So a one-wave gate kernel runs in front of k+1 on its
+  // stream and ends once k's queue counter has left its base -- a wave of k has taken a
+  // unit, so k has resident waves before k+1 has any, whatever the history.
+  const bool overlap = c->overlap_on && q.queue && c->prev_queue && c->prev_W == a.W &&
+                       !l.serial && !a.trace && c->prev_slot >= 0;
+  if (overlap) {
+    q.ptag = c->prev_tag;
+  } else if (c->prev_slot >= 0) {
+    HIPCHK(hipStreamWaitEvent(s, c->ev[c->prev_slot][1], 0));
+  }
+  if (q.hold) HIPCHK(hipMemsetAsync(q.hold, 0, sizeof(unsigned long long), s));
   // progress balancing (olpe_gibbs_kernel): on by default for a 16-wave 2-source FAST
   // launch that runs its walkers whole in one round, which ends on its slowest wave
   // (configs[1]: +2 % over the 12-wave sampler; profiles/r02/ab_w16.log)
@@ -1055,7 +1124,7 @@ int launch_gibbs_t(olpe_ctx *c, const GibbsArgs &a) {
             : (LDS && FAST && NSRC == 2 && WPB == 16 && q.units == 1 &&
                a.W <= (long long)resident * WPB) ? 1 : 0;
   c->last_units = q.units;
-  if (q.units > 1) c->units_used = true;
+  if (q.units > 1 || overlap) c->units_used = true;
   // a hand-off waits at most for one chunk of the same walker (its predecessor) to run:
   // bound a chunk's time generously -- 8 ns per pixel-Gaussian per iteration, ~30x the
   // slowest sampler (EXACT, 3 sources, 128x128) -- and never below 30 s
@@ -1067,24 +1136,42 @@ int launch_gibbs_t(olpe_ctx *c, const GibbsArgs &a) {
                        : (unsigned long long)std::min(std::max(ticks, 3e9), 1e15);
     c->wait_limit_s = (double)q.wait_ticks * 1e-8;
   }
-  hipLaunchKernelGGL(k, dim3(blocks), dim3(WPB * 64), shm, c->stream, q);
+  if (overlap) {
+    hipLaunchKernelGGL(olpe_overlap_gate_kernel, dim3(1), dim3(64), 0, s, c->prev_qptr,
+                       c->prev_qbase, q.uerr, q.wait_ticks);
+    HIPCHK(hipGetLastError());
+  }
+  // the launch's time (olpe_kernel_times) starts behind everything it waits for
+  HIPCHK(hipEventRecord(c->ev[l.slot][0], s));
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(WPB * 64), shm, s, q);
   HIPCHK(hipGetLastError());
-  // the launch takes W * units + (its waves) values off the counter (the ring sampler:
-  // one per batch of WPB units + one per workgroup): the next launch's base (advanced
-  // only once the launch is in the stream)
+  c->prev_qptr = q.queue;
+  c->prev_qbase = q.qbase;
+  HIPCHK(hipEventRecord(c->ev[l.slot][1], s));
+  HIPCHK(hipEventRecord(c->ev_tail[p], s));
+  c->pend = true;
+  c->ev_ovl[l.slot] = overlap;
+  c->overlaps += overlap ? 1 : 0;
+  // the launch takes W * units + (its waves) values off its parity's counter (the ring
+  // sampler: one per batch of WPB units + one per workgroup): that parity's next base
+  // (advanced only once the launch is in the stream)
   if (q.queue) {
     const unsigned long long tot = (unsigned long long)a.W * (unsigned long long)q.units;
-    c->qbase += RING ? (tot + WPB - 1) / WPB + blocks : tot + (unsigned long long)blocks * WPB;
+    c->qbase2[p] += RING ? (tot + WPB - 1) / WPB + blocks : tot + (unsigned long long)blocks * WPB;
   }
+  c->prev_queue = q.queue != nullptr;
+  c->prev_W = a.W;
+  c->prev_tag = q.utag + (unsigned)q.units;
+  c->prev_slot = l.slot;
   return OLPE_OK;
 }
 
-template <int NSRC, bool FAST> int launch_gibbs_m(olpe_ctx *c, const GibbsArgs &a) {
+template <int NSRC, bool FAST> int launch_gibbs_m(olpe_ctx *c, const GibbsArgs &a, const LaunchSlot &l) {
   if (c->lds_img) {
     switch (c->n) {
       // 12 waves at 32x32 as well (168 VGPRs: no spills; 3-source +77 %, 2-source +1 %
       // over 16)
-      case 32: return launch_gibbs_t<NSRC, 32, true, 12, FAST>(c, a);
+      case 32: return launch_gibbs_t<NSRC, 32, true, 12, FAST>(c, a, l);
       case 64: {
         // 12 waves per workgroup (168 VGPRs: four-row update and shape-table prefetch
         // without spills, 3 waves per SIMD with the walker queue keeping them busy);
@@ -1103,11 +1190,11 @@ template <int NSRC, bool FAST> int launch_gibbs_m(olpe_ctx *c, const GibbsArgs &
                 : (NSRC == 2 && (!FAST || a.W >= 8 * r16 || (a.W > r12 && a.W <= r16)))
                       ? 16 : 12;
         if (wpb == 16 && lds_bytes(c, 16) > 160 * 1024) wpb = 12;
-        if (wpb == 8) return launch_gibbs_t<NSRC, 64, true, 8, FAST>(c, a);
-        if (wpb == 12) return launch_gibbs_t<NSRC, 64, true, 12, FAST>(c, a);
-        return launch_gibbs_t<NSRC, 64, true, 16, FAST>(c, a);
+        if (wpb == 8) return launch_gibbs_t<NSRC, 64, true, 8, FAST>(c, a, l);
+        if (wpb == 12) return launch_gibbs_t<NSRC, 64, true, 12, FAST>(c, a, l);
+        return launch_gibbs_t<NSRC, 64, true, 16, FAST>(c, a, l);
       }
-      default: return launch_gibbs_t<NSRC, 0, true, 16, FAST>(c, a);
+      default: return launch_gibbs_t<NSRC, 0, true, 16, FAST>(c, a, l);
     }
   }
   if (c->n == 128) {
@@ -1117,22 +1204,22 @@ template <int NSRC, bool FAST> int launch_gibbs_m(olpe_ctx *c, const GibbsArgs &
       // (two 6-wave workgroups per CU with rings of their own -- their control phases
       // apart -- ran at 0.65x: the dispatcher does not pack two of them on a CU)
       if (c->ring_wpb && c->queue_on && c->d_queue && c->d_uflag) {
-        return launch_gibbs_t<NSRC, 128, false, 12, FAST>(c, a);
+        return launch_gibbs_t<NSRC, 128, false, 12, FAST>(c, a, l);
       }
     }
-    return launch_gibbs_t<NSRC, 128, false, 4, FAST>(c, a);
+    return launch_gibbs_t<NSRC, 128, false, 4, FAST>(c, a, l);
   }
   // large cutouts (a full 1024 x 1024 NIRC2 frame): one wave per workgroup once four
   // waves' row tables (n x 2 NSRC doubles each) no longer fit the LDS; olpe_create
   // rejects sides where even one does not
-  if (lds_bytes(c, 4) > 160 * 1024) return launch_gibbs_t<NSRC, 0, false, 1, FAST>(c, a);
-  return launch_gibbs_t<NSRC, 0, false, 4, FAST>(c, a);
+  if (lds_bytes(c, 4) > 160 * 1024) return launch_gibbs_t<NSRC, 0, false, 1, FAST>(c, a, l);
+  return launch_gibbs_t<NSRC, 0, false, 4, FAST>(c, a, l);
 }
 
-int launch_gibbs(olpe_ctx *c, const GibbsArgs &a) {
+int launch_gibbs(olpe_ctx *c, const GibbsArgs &a, const LaunchSlot &l) {
   const bool fast = c->eval_mode == OLPE_EVAL_FAST;
-  if (c->nsrc == 2) return fast ? launch_gibbs_m<2, true>(c, a) : launch_gibbs_m<2, false>(c, a);
-  return fast ? launch_gibbs_m<3, true>(c, a) : launch_gibbs_m<3, false>(c, a);
+  if (c->nsrc == 2) return fast ? launch_gibbs_m<2, true>(c, a, l) : launch_gibbs_m<2, false>(c, a, l);
+  return fast ? launch_gibbs_m<3, true>(c, a, l) : launch_gibbs_m<3, false>(c, a, l);
 }
 
 int ensure_ensemble(olpe_ctx *c, int W) {
@@ -1148,11 +1235,11 @@ int ensure_ensemble(olpe_ctx *c, int W) {
   if ((rc = dev_alloc(&c->d_hasg, (size_t)W))) return rc;
   if ((rc = dev_alloc(&c->d_done, (size_t)W))) return rc;
   if ((rc = dev_alloc(&c->d_uflag, (size_t)W))) return rc;
-  HIPCHK(hipMemsetAsync(c->d_uflag, 0, (size_t)W * sizeof(unsigned), c->stream));
-  HIPCHK(hipMemsetAsync(c->d_state, 0, (size_t)W * c->ps * sizeof(double), c->stream));
-  HIPCHK(hipMemsetAsync(c->d_tries, 0, (size_t)W * c->np * sizeof(uint32_t), c->stream));
-  HIPCHK(hipMemsetAsync(c->d_acc, 0, (size_t)W * c->np * sizeof(uint32_t), c->stream));
-  HIPCHK(hipMemsetAsync(c->d_done, 0xff, (size_t)W * sizeof(long long), c->stream));
+  HIPCHK(hipMemsetAsync(c->d_uflag, 0, (size_t)W * sizeof(unsigned), olpe_main(c)));
+  HIPCHK(hipMemsetAsync(c->d_state, 0, (size_t)W * c->ps * sizeof(double), olpe_main(c)));
+  HIPCHK(hipMemsetAsync(c->d_tries, 0, (size_t)W * c->np * sizeof(uint32_t), olpe_main(c)));
+  HIPCHK(hipMemsetAsync(c->d_acc, 0, (size_t)W * c->np * sizeof(uint32_t), olpe_main(c)));
+  HIPCHK(hipMemsetAsync(c->d_done, 0xff, (size_t)W * sizeof(long long), olpe_main(c)));
   c->W = W;
   c->seeded = false;
   c->count = 0;
@@ -1163,10 +1250,47 @@ int ensure_ensemble(olpe_ctx *c, int W) {
 
 }  // namespace
 
+// The two ordering classes of a context's device work.  Sampler launches
+// and the moments fold run on the two sampler streams; everything else is main class and
+// takes its stream from here, which first puts that stream behind all of them.
+hipStream_t olpe_main(olpe_ctx *c) {
+  if (c->pend) {
+    for (hipEvent_t e : c->ev_tail)
+      if (e) (void)hipStreamWaitEvent(c->stream, e, 0);
+    c->pend = false;
+  }
+  c->main_dirty = true;
+  return c->stream;
+}
+
+// s behind the main-class work enqueued so far
+static int follow_main(olpe_ctx *c, hipStream_t s) {
+  if (!c->main_dirty) return OLPE_OK;
+  HIPCHK(hipEventRecord(c->ev_main, c->stream));
+  HIPCHK(hipStreamWaitEvent(s, c->ev_main, 0));
+  return OLPE_OK;
+}
+
+int olpe_fold_stream(olpe_ctx *c, hipStream_t *s) {
+  *s = c->sstream[c->par];
+  int rc;
+  if ((rc = follow_main(c, *s))) return rc;
+  HIPCHK(hipStreamWaitEvent(*s, c->ev_fold, 0));
+  return OLPE_OK;
+}
+
+int olpe_fold_done(olpe_ctx *c) {
+  const hipStream_t s = c->sstream[c->par];
+  HIPCHK(hipEventRecord(c->ev_fold, s));
+  HIPCHK(hipEventRecord(c->ev_tail[c->par], s));
+  c->pend = true;
+  return OLPE_OK;
+}
+
 // the default tables into the context's widths (and, at creation, into the copy the tuner
 // clamps against), behind whatever the context's stream holds
 int olpe_widths_defaults(olpe_ctx *c, bool with_base) {
-  hipLaunchKernelGGL(widths_default_kernel, dim3(1), dim3(64), 0, c->stream, c->nsrc, c->d_widths,
+  hipLaunchKernelGGL(widths_default_kernel, dim3(1), dim3(64), 0, olpe_main(c), c->nsrc, c->d_widths,
                      with_base ? c->d_wdef : nullptr);
   HIPCHK(hipGetLastError());
   return OLPE_OK;
@@ -1306,10 +1430,17 @@ int olpe_create(const void *image, int image_dtype, const void *pois2, double re
     hDW[0] = make_double2(NAN, NAN);
   }
   int rc;
+  // the main-class stream and the two sampler streams (three queues: within the default
+  // of four a process opens)
   hipError_t e1 = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+  for (auto &s : c->sstream)
+    if (e1 == hipSuccess) e1 = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+  hipEvent_t *order[] = {&c->ev_tail[0], &c->ev_tail[1], &c->ev_fold, &c->ev_main};
+  for (hipEvent_t *e : order)
+    if (e1 == hipSuccess) e1 = hipEventCreateWithFlags(e, hipEventDisableTiming);
   if (e1 != hipSuccess) {
-    delete c;
-    return set_err(OLPE_EHIP, "hipStreamCreate: %s", hipGetErrorString(e1));
+    olpe_destroy(c);
+    return set_err(OLPE_EHIP, "stream / event creation: %s", hipGetErrorString(e1));
   }
   for (auto &pair : c->ev)
     for (auto &ev : pair)
@@ -1317,13 +1448,14 @@ int olpe_create(const void *image, int image_dtype, const void *pois2, double re
   // the collectives' words (olpe_comm_setup), allocated here so that olpe_comm_init has
   // nothing to allocate that could fail on one rank while the others wait for it
   if ((rc = dev_alloc(&c->d_DE, npix)) || (rc = dev_alloc(&c->d_DW, npix)) ||
-      (rc = dev_alloc(&c->d_queue, 5)) || (rc = olpe_comm_setup(c))) {
+      (rc = dev_alloc(&c->d_queue, 7)) || (rc = olpe_comm_setup(c))) {
     olpe_destroy(c);
     return rc;
   }
-  // [0] the queue counter, [1] the hand-off error word, [2..3] hand-off statistics
-  // (unit_wait), [4] the hand-off hold word (olpe_test_hold_handoff)
-  if (hipMemset(c->d_queue, 0, 5 * sizeof(unsigned long long)) != hipSuccess ||
+  // [0] the queue counter of even launches, [1] the hand-off error word, [2..3] hand-off
+  // statistics (unit_wait), [4] the hand-off hold word (olpe_test_hold_handoff) of even
+  // launches, [5] / [6] the odd launches' counter and hold word
+  if (hipMemset(c->d_queue, 0, 7 * sizeof(unsigned long long)) != hipSuccess ||
       hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, device) !=
           hipSuccess || c->n_cu <= 0) {
     olpe_destroy(c);
@@ -1338,6 +1470,8 @@ int olpe_create(const void *image, int image_dtype, const void *pois2, double re
     }
     c->units_override = p;
   }
+  // 0: every launch waits for its predecessor's end (A/B, tests); on by default
+  if (const char *e = getenv("OLPE_OVERLAP")) c->overlap_on = atoi(e) != 0;
   if (const char *e = getenv("OLPE_RING")) {                                // A/B, tests
     const int v = atoi(e);
     if (v != 0 && v != 12) {
@@ -1363,7 +1497,7 @@ int olpe_create(const void *image, int image_dtype, const void *pois2, double re
     olpe_destroy(c);
     return rc;
   }
-  if (hipStreamSynchronize(c->stream) != hipSuccess) {
+  if (hipStreamSynchronize(olpe_main(c)) != hipSuccess) {
     olpe_destroy(c);
     return set_err(OLPE_EHIP, "filling in the default jump widths failed");
   }
@@ -1374,11 +1508,13 @@ int olpe_create(const void *image, int image_dtype, const void *pois2, double re
 void olpe_destroy(olpe_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
+  for (hipStream_t s : c->sstream)
+    if (s) (void)hipStreamSynchronize(s);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   olpe_comm_release(c);
   void *ptrs[] = {c->d_DE, c->d_DW, c->d_state, c->d_tries, c->d_acc,
                   c->d_mt, c->d_mtpos, c->d_gauss, c->d_hasg,  c->d_done,
-                  c->d_chain, c->d_trace, c->d_scratch, c->d_scratch2, c->d_queue,
+                  c->d_chain2[0], c->d_chain2[1], c->d_trace, c->d_scratch, c->d_scratch2, c->d_queue,
                   c->d_gather, c->d_uflag, c->d_mmean, c->d_mm2, c->d_mpart, c->d_check,
                   c->d_widths, c->d_wdef, c->d_tune};
   for (void *p : ptrs)
@@ -1386,6 +1522,10 @@ void olpe_destroy(olpe_ctx *c) {
   for (auto &pair : c->ev)
     for (auto &ev : pair)
       if (ev) (void)hipEventDestroy(ev);
+  for (hipEvent_t e : {c->ev_tail[0], c->ev_tail[1], c->ev_fold, c->ev_main})
+    if (e) (void)hipEventDestroy(e);
+  for (hipStream_t s : c->sstream)
+    if (s) (void)hipStreamDestroy(s);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
@@ -1409,7 +1549,7 @@ static int eval_batch(olpe_ctx *c, const double *params, int W, double *out, boo
   if (c->scratch_cap < pin) c->scratch_cap = pin;
   if (c->scratch2_cap < pout && (rc = dev_alloc(&c->d_scratch2, pout))) return rc;
   if (c->scratch2_cap < pout) c->scratch2_cap = pout;
-  HIPCHK(hipMemcpyAsync(c->d_scratch, params, pin * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->d_scratch, params, pin * 8, hipMemcpyHostToDevice, olpe_main(c)));
   // four vectors per workgroup, fewer where their row tables would not fit the LDS
   int wpb = 4;
   while (wpb > 1 && (size_t)wpb * vtab_bytes(c->n, c->nsrc) + kEtabBytes > 160 * 1024) wpb /= 2;
@@ -1435,22 +1575,22 @@ static int eval_batch(olpe_ctx *c, const double *params, int W, double *out, boo
   }
   if (c->nsrc == 2) {
     if (write)
-      hipLaunchKernelGGL((olpe_eval_kernel<2, true>), grid, block, shm, c->stream, fast ? c->d_DW : c->d_DE,
+      hipLaunchKernelGGL((olpe_eval_kernel<2, true>), grid, block, shm, olpe_main(c), fast ? c->d_DW : c->d_DE,
                          c->n, c->bkgd_mode, fast, c->d_scratch, W, c->d_scratch2);
     else
-      hipLaunchKernelGGL((olpe_eval_kernel<2, false>), grid, block, shm, c->stream, fast ? c->d_DW : c->d_DE,
+      hipLaunchKernelGGL((olpe_eval_kernel<2, false>), grid, block, shm, olpe_main(c), fast ? c->d_DW : c->d_DE,
                          c->n, c->bkgd_mode, fast, c->d_scratch, W, c->d_scratch2);
   } else {
     if (write)
-      hipLaunchKernelGGL((olpe_eval_kernel<3, true>), grid, block, shm, c->stream, fast ? c->d_DW : c->d_DE,
+      hipLaunchKernelGGL((olpe_eval_kernel<3, true>), grid, block, shm, olpe_main(c), fast ? c->d_DW : c->d_DE,
                          c->n, c->bkgd_mode, fast, c->d_scratch, W, c->d_scratch2);
     else
-      hipLaunchKernelGGL((olpe_eval_kernel<3, false>), grid, block, shm, c->stream, fast ? c->d_DW : c->d_DE,
+      hipLaunchKernelGGL((olpe_eval_kernel<3, false>), grid, block, shm, olpe_main(c), fast ? c->d_DW : c->d_DE,
                          c->n, c->bkgd_mode, fast, c->d_scratch, W, c->d_scratch2);
   }
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, c->d_scratch2, pout * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(out, c->d_scratch2, pout * 8, hipMemcpyDeviceToHost, olpe_main(c)));
+  HIPCHK(hipStreamSynchronize(olpe_main(c)));
   return OLPE_OK;
 }
 
@@ -1469,11 +1609,11 @@ int olpe_seed(olpe_ctx *c, const uint32_t *seeds, int W) {
   if ((rc = ensure_ensemble(c, W))) return rc;
   uint32_t *ds = nullptr;
   if ((rc = dev_alloc(&ds, (size_t)W))) return rc;
-  HIPCHK(hipMemcpyAsync(ds, seeds, (size_t)W * 4, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(olpe_seed_kernel, dim3((W + 255) / 256), dim3(256), 0, c->stream, ds, W,
+  HIPCHK(hipMemcpyAsync(ds, seeds, (size_t)W * 4, hipMemcpyHostToDevice, olpe_main(c)));
+  hipLaunchKernelGGL(olpe_seed_kernel, dim3((W + 255) / 256), dim3(256), 0, olpe_main(c), ds, W,
                      c->d_mt, c->d_mtpos, c->d_hasg, c->d_gauss);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(olpe_main(c)));
   (void)hipFree(ds);
   c->seeded = true;
   c->mom_n = 0;                  // a new run: no rows folded into the moments yet
@@ -1502,8 +1642,8 @@ static int counters_to_dev(olpe_ctx *c, const double *h, uint32_t *d) {
         return set_err(OLPE_EINVAL, "counter %zu out of range (%g)", i, h[i]);
       t[i] = (uint32_t)h[i];
     }
-  HIPCHK(hipMemcpyAsync(d, t.data(), m * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(d, t.data(), m * 4, hipMemcpyHostToDevice, olpe_main(c)));
+  HIPCHK(hipStreamSynchronize(olpe_main(c)));
   return OLPE_OK;
 }
 
@@ -1520,14 +1660,14 @@ int olpe_state_set(olpe_ctx *c, const double *state, const double *tries,
   if (!c || !state) return set_err(OLPE_EINVAL, "NULL argument");
   if (!c->d_state) return set_err(OLPE_ESTATE, "call olpe_seed first");
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(olpe_main(c)));
   HIPCHK(hipMemcpyAsync(c->d_state, state, (size_t)c->W * c->ps * 8, hipMemcpyHostToDevice,
-                        c->stream));
+                        olpe_main(c)));
   int rc;
   if ((rc = counters_to_dev(c, tries, c->d_tries))) return rc;
   if ((rc = counters_to_dev(c, accepts, c->d_acc))) return rc;
-  HIPCHK(hipMemsetAsync(c->d_done, 0xff, (size_t)c->W * sizeof(long long), c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemsetAsync(c->d_done, 0xff, (size_t)c->W * sizeof(long long), olpe_main(c)));
+  HIPCHK(hipStreamSynchronize(olpe_main(c)));
   return OLPE_OK;
 }
 
@@ -1535,7 +1675,7 @@ int olpe_state_get(olpe_ctx *c, double *state, double *tries, double *accepts) {
   if (!c) return set_err(OLPE_EINVAL, "NULL ctx");
   if (!c->d_state) return set_err(OLPE_ESTATE, "no ensemble");
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(olpe_main(c)));
   if (state)
     HIPCHK(hipMemcpy(state, c->d_state, (size_t)c->W * c->ps * 8, hipMemcpyDeviceToHost));
   int rc;
@@ -1567,12 +1707,16 @@ int olpe_run(olpe_ctx *c, long long n_iters, long long burn_in, int record_strid
     }
   }
   int rc;
+  // this launch's parity: its stream, queue counter and chain buffer (the other
+  // parity's launch and its fold may still be in flight; they touch none of these)
+  const int p = c->par ^ 1;
   const size_t chain_need = (size_t)c->W * nrows * c->ps;
-  if (chain_need > c->chain_cap) {
-    if ((rc = dev_alloc(&c->d_chain, chain_need))) return rc;
-    c->chain_cap = chain_need;
+  if (chain_need > c->chain_cap2[p]) {
+    // (hipFree waits for the device: nothing in flight reads the buffer that grows)
+    c->chain_cap2[p] = 0;
+    if ((rc = dev_alloc(&c->d_chain2[p], chain_need))) return rc;
+    c->chain_cap2[p] = chain_need;
   }
-  c->chain_rows = nrows;
   const size_t trace_need = c->trace_on ? (size_t)c->W * n_iters * kTraceF : 0;
   if (trace_need > c->trace_cap) {
     if ((rc = dev_alloc(&c->d_trace, trace_need))) return rc;
@@ -1599,15 +1743,25 @@ int olpe_run(olpe_ctx *c, long long n_iters, long long burn_in, int record_strid
   a.stride = nrows > 0 ? record_stride : 0;
   a.row0 = row0;
   a.nrows = nrows;
-  a.chain = c->d_chain;
+  a.chain = c->d_chain2[p];
   a.accept_min = accept_min;
   a.trace = c->trace_on ? c->d_trace : nullptr;
   a.widths = c->d_widths;
-  hipEvent_t *ev = c->ev[c->launches % olpe_ctx::kRing];
-  if (!ev[0] || !ev[1]) return set_err(OLPE_EHIP, "launch events were not created");
-  HIPCHK(hipEventRecord(ev[0], c->stream));
-  if ((rc = launch_gibbs(c, a))) return rc;
-  HIPCHK(hipEventRecord(ev[1], c->stream));
+  const LaunchSlot l{(int)(c->launches % olpe_ctx::kSlots), c->main_dirty};
+  if (!c->ev[l.slot][0] || !c->ev[l.slot][1])
+    return set_err(OLPE_EHIP, "launch events were not created");
+  // main-class work enqueued since the previous launch (a new state, new widths, a
+  // step-3 fold still reading the rows, ...): the launch follows it
+  if ((rc = follow_main(c, c->sstream[p]))) return rc;
+  c->par = p;
+  if ((rc = launch_gibbs(c, a, l))) {
+    c->par = p ^ 1;
+    return rc;
+  }
+  c->main_dirty = false;
+  c->d_chain = c->d_chain2[p];
+  c->chain_cap = c->chain_cap2[p];
+  c->chain_rows = nrows;
   ++c->launches;
   c->count = c1;
   if (nrec_out) *nrec_out = nrows;
@@ -1617,7 +1771,7 @@ int olpe_run(olpe_ctx *c, long long n_iters, long long burn_in, int record_strid
 int olpe_chain_read(olpe_ctx *c, double *chain_out) {
   if (!c || !chain_out) return set_err(OLPE_EINVAL, "NULL argument");
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(olpe_main(c)));
   const size_t m = (size_t)c->W * c->chain_rows * c->ps;
   if (m) HIPCHK(hipMemcpy(chain_out, c->d_chain, m * 8, hipMemcpyDeviceToHost));
   return check_units(c);
@@ -1639,7 +1793,7 @@ int olpe_done_at(olpe_ctx *c, long long *done_at) {
   if (!c || !done_at) return set_err(OLPE_EINVAL, "NULL argument");
   if (!c->d_done) return set_err(OLPE_ESTATE, "no ensemble");
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(olpe_main(c)));
   HIPCHK(hipMemcpy(done_at, c->d_done, (size_t)c->W * 8, hipMemcpyDeviceToHost));
   return check_units(c);
 }
@@ -1663,7 +1817,7 @@ int olpe_rng_get(olpe_ctx *c, uint32_t *mt_state, double *gauss_cache) {
   if (!c) return set_err(OLPE_EINVAL, "NULL ctx");
   if (!c->d_mt) return set_err(OLPE_ESTATE, "no ensemble");
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(olpe_main(c)));
   const int W = c->W;
   if (mt_state) {
     std::vector<uint32_t> key((size_t)W * MT_N);
@@ -1692,7 +1846,7 @@ int olpe_rng_set(olpe_ctx *c, const uint32_t *mt_state, const double *gauss_cach
   if (!c || !mt_state || !gauss_cache) return set_err(OLPE_EINVAL, "NULL argument");
   if (!c->d_mt) return set_err(OLPE_ESTATE, "no ensemble (call olpe_seed)");
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(olpe_main(c)));
   const int W = c->W;
   std::vector<uint32_t> key((size_t)W * MT_N);
   std::vector<int> pos(W), h(W);
@@ -1722,14 +1876,14 @@ int olpe_rng_stream(olpe_ctx *c, int kind, int n, void *out) {
   void *d = nullptr;
   HIPCHK(hipMalloc(&d, bytes));
   if (c->np == 16)
-    hipLaunchKernelGGL(olpe_stream_kernel<16>, dim3(c->W), dim3(64), 0, c->stream, c->d_mt,
+    hipLaunchKernelGGL(olpe_stream_kernel<16>, dim3(c->W), dim3(64), 0, olpe_main(c), c->d_mt,
                        c->d_mtpos, c->d_hasg, c->d_gauss, c->W, kind, n, d);
   else
-    hipLaunchKernelGGL(olpe_stream_kernel<19>, dim3(c->W), dim3(64), 0, c->stream, c->d_mt,
+    hipLaunchKernelGGL(olpe_stream_kernel<19>, dim3(c->W), dim3(64), 0, olpe_main(c), c->d_mt,
                        c->d_mtpos, c->d_hasg, c->d_gauss, c->W, kind, n, d);
   hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, olpe_main(c));
+  if (e == hipSuccess) e = hipStreamSynchronize(olpe_main(c));
   (void)hipFree(d);
   if (e != hipSuccess) return set_err(OLPE_EHIP, "rng stream: %s", hipGetErrorString(e));
   return OLPE_OK;
@@ -1741,25 +1895,42 @@ int olpe_test_hold_handoff(olpe_ctx *c, int on) {
   return OLPE_OK;
 }
 
+int olpe_test_overlaps(olpe_ctx *c, long long *count) {
+  if (!c || !count) return set_err(OLPE_EINVAL, "NULL argument");
+  *count = c->overlaps;
+  return OLPE_OK;
+}
+
 int olpe_test_chain_set(olpe_ctx *c, const double *chain, long long nrec) {
   if (!c || nrec < 0 || (nrec > 0 && !chain)) return set_err(OLPE_EINVAL, "bad argument");
   if (!c->d_state || !c->seeded) return set_err(OLPE_ESTATE, "call olpe_seed first");
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipStreamSynchronize(c->stream));   // a queued fold may still read the old rows
+  HIPCHK(hipStreamSynchronize(olpe_main(c)));   // a queued fold may still read the old rows
   int rc;
   const size_t chain_need = (size_t)c->W * nrec * c->ps;
-  if (chain_need > c->chain_cap) {
+  // (the rows stand in for a launch of the last launch's parity: its buffer)
+  const int p = c->par;
+  if (chain_need > c->chain_cap2[p]) {
+    c->chain_cap2[p] = 0;
+    c->d_chain = nullptr;
     c->chain_cap = 0;
-    if ((rc = dev_alloc(&c->d_chain, chain_need))) return rc;
-    c->chain_cap = chain_need;
+    c->chain_rows = 0;
+    if ((rc = dev_alloc(&c->d_chain2[p], chain_need))) return rc;
+    c->chain_cap2[p] = chain_need;
   }
-  hipEvent_t *ev = c->ev[c->launches % olpe_ctx::kRing];
+  c->d_chain = c->d_chain2[p];
+  c->chain_cap = c->chain_cap2[p];
+  const int slot = (int)(c->launches % olpe_ctx::kSlots);
+  hipEvent_t *ev = c->ev[slot];
   if (!ev[0] || !ev[1]) return set_err(OLPE_EHIP, "launch events were not created");
-  HIPCHK(hipEventRecord(ev[0], c->stream));
+  c->ev_ovl[slot] = false;
+  c->prev_slot = slot;          // the next launch follows this copy, and overlaps nothing
+  c->prev_queue = false;
+  HIPCHK(hipEventRecord(ev[0], olpe_main(c)));
   if (chain_need)
-    HIPCHK(hipMemcpyAsync(c->d_chain, chain, chain_need * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipEventRecord(ev[1], c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));   // the caller's buffer is free on return
+    HIPCHK(hipMemcpyAsync(c->d_chain, chain, chain_need * 8, hipMemcpyHostToDevice, olpe_main(c)));
+  HIPCHK(hipEventRecord(ev[1], olpe_main(c)));
+  HIPCHK(hipStreamSynchronize(olpe_main(c)));   // the caller's buffer is free on return
   c->chain_rows = nrec;
   ++c->launches;
   return OLPE_OK;
@@ -1774,7 +1945,7 @@ int olpe_trace_enable(olpe_ctx *c, int on) {
 int olpe_trace_read(olpe_ctx *c, double *out) {
   if (!c || !out) return set_err(OLPE_EINVAL, "NULL argument");
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(olpe_main(c)));
   const size_t m = (size_t)c->W * c->trace_iters * kTraceF;
   if (m) HIPCHK(hipMemcpy(out, c->d_trace, m * 8, hipMemcpyDeviceToHost));
   return OLPE_OK;
@@ -1783,14 +1954,14 @@ int olpe_trace_read(olpe_ctx *c, double *out) {
 int olpe_sync(olpe_ctx *c) {
   if (!c) return set_err(OLPE_EINVAL, "NULL ctx");
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(olpe_main(c)));
   return check_units(c);
 }
 
 int olpe_unit_stats(olpe_ctx *c, long long *out) {
   if (!c || !out) return set_err(OLPE_EINVAL, "NULL argument");
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(olpe_main(c)));
   unsigned long long v[2] = {0, 0};
   HIPCHK(hipMemcpy(v, c->d_queue + 2, sizeof(v), hipMemcpyDeviceToHost));
   out[0] = (long long)v[0];
@@ -1810,11 +1981,21 @@ int olpe_kernel_times(olpe_ctx *c, int n, double *ms_out) {
     return set_err(OLPE_EINVAL, "n = %d: 1..min(%d, launches so far = %lld)", n,
                    olpe_ctx::kRing, c->launches);
   HIPCHK(hipSetDevice(c->device));
+  // A launch's time runs to its end event from the later of its start event and, where
+  // it overlapped its predecessor, that launch's end event: the mean over back-to-back
+  // launches is then the time per launch, and without overlap it is the launch's own span.
   for (int i = 0; i < n; ++i) {
-    hipEvent_t *ev = c->ev[(c->launches - n + i) % olpe_ctx::kRing];
+    const long long j = c->launches - n + i;
+    const int slot = (int)(j % olpe_ctx::kSlots);
+    hipEvent_t *ev = c->ev[slot];
     HIPCHK(hipEventSynchronize(ev[1]));
     float f = 0.f;
     HIPCHK(hipEventElapsedTime(&f, ev[0], ev[1]));
+    if (c->ev_ovl[slot] && j > 0) {
+      float g = 0.f;
+      HIPCHK(hipEventElapsedTime(&g, c->ev[(j - 1) % olpe_ctx::kSlots][1], ev[1]));
+      if (g > 0.f && g < f) f = g;
+    }
     ms_out[i] = f;
   }
   return OLPE_OK;

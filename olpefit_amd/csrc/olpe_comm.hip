@@ -78,7 +78,7 @@ int abort_comm(olpe_ctx *c, const char *fmt, ...) {
   c->comm_aborted = true;
   // the aborted kernels see RCCL's abort flag and exit; bounded all the same
   const double t0 = now_s();
-  while (hipStreamQuery(c->stream) == hipErrorNotReady && now_s() - t0 < 10.0)
+  while (hipStreamQuery(olpe_main(c)) == hipErrorNotReady && now_s() - t0 < 10.0)
     std::this_thread::sleep_for(std::chrono::microseconds(200));
   (void)hipGetLastError();
   return set_err(OLPE_ECOMM, "%s", msg);
@@ -124,13 +124,13 @@ int settle(olpe_ctx *c, ncclResult_t r, const char *what) {
 // that died or left) ends in an abort here, not in a hang.
 int comm_wait(olpe_ctx *c, const char *what) {
   if (!c->comm) {
-    const hipError_t e = hipStreamSynchronize(c->stream);
+    const hipError_t e = hipStreamSynchronize(olpe_main(c));
     return e == hipSuccess ? OLPE_OK : set_err(OLPE_EHIP, "%s: %s", what, hipGetErrorString(e));
   }
   const double t0 = now_s();
   int spins = 0;
   for (;;) {
-    const hipError_t e = hipStreamQuery(c->stream);
+    const hipError_t e = hipStreamQuery(olpe_main(c));
     if (e == hipSuccess) return OLPE_OK;
     if (e != hipErrorNotReady) return set_err(OLPE_EHIP, "%s: %s", what, hipGetErrorString(e));
     ncclResult_t a = ncclSuccess;
@@ -165,7 +165,7 @@ struct Rccl {
   }
   int copy(void *dst, const void *src, size_t n, hipMemcpyKind kind, proto::Site s) {
     if (forced(s)) return fail(s);
-    const hipError_t e = hipMemcpyAsync(dst, src, n, kind, c->stream);
+    const hipError_t e = hipMemcpyAsync(dst, src, n, kind, olpe_main(c));
     return e == hipSuccess ? OLPE_OK
                            : set_err(OLPE_EHIP, "%s: %s", proto::site_name(s), hipGetErrorString(e));
   }
@@ -180,7 +180,7 @@ struct Rccl {
     if (c->comm_aborted) return aborted(s);
     if (!c->comm) return send == recv ? OLPE_OK : copy(recv, send, n * sizeof(T),
                                                        hipMemcpyDeviceToDevice, s);
-    return settle(c, ncclAllReduce(send, recv, n, t, op, (ncclComm_t)c->comm, c->stream),
+    return settle(c, ncclAllReduce(send, recv, n, t, op, (ncclComm_t)c->comm, olpe_main(c)),
                   proto::site_name(s));
   }
   int allreduce_max_i64(const long long *s, long long *r, size_t n, proto::Site site) {
@@ -192,7 +192,7 @@ struct Rccl {
   int allgather_f64(const double *s, double *r, size_t n, proto::Site site) {
     if (c->comm_aborted) return aborted(site);
     if (!c->comm) return copy(r, s, n * sizeof(double), hipMemcpyDeviceToDevice, site);
-    return settle(c, ncclAllGather(s, r, n, ncclDouble, (ncclComm_t)c->comm, c->stream),
+    return settle(c, ncclAllGather(s, r, n, ncclDouble, (ncclComm_t)c->comm, olpe_main(c)),
                   proto::site_name(site));
   }
   int wait(proto::Site s) { return comm_wait(c, proto::site_name(s)); }

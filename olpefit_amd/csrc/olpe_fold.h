@@ -114,25 +114,29 @@ inline void fold_mark(FoldBase *b, const olpe_ctx *c) {
   b->last_launch = c->launches;
 }
 
-// c->stream is behind the launch already; this puts it behind whatever the object has in
-// flight as well (an earlier fold on another context's stream included: drain() then
+// the context's main-class stream (olpe_main: behind every sampler launch and moments
+// fold); the folds hold the context const, the stream bookkeeping is not part of that
+inline hipStream_t main_stream(const olpe_ctx *c) { return olpe_main(const_cast<olpe_ctx *>(c)); }
+
+// The main stream is behind the launch already; this puts it behind whatever the object has
+// in flight as well (an earlier fold on another context's stream included: drain() then
 // waits for one event only)
 inline int fold_enter(FoldBase *b, const olpe_ctx *c) {
   int rc;
   if ((rc = wait_pending(b))) return rc;
   HIPCHK(hipEventRecord(b->ev, b->stream));
-  HIPCHK(hipStreamWaitEvent(c->stream, b->ev, 0));
+  HIPCHK(hipStreamWaitEvent(main_stream(c), b->ev, 0));
   return OLPE_OK;
 }
 
 inline int fold_leave(FoldBase *b, const olpe_ctx *c) {
-  HIPCHK(hipEventRecord(b->ev, c->stream));
+  HIPCHK(hipEventRecord(b->ev, main_stream(c)));
   b->ev_pending = true;
   return OLPE_OK;
 }
 
-// The fold's place on the sampler's stream: the launch counts as folded from here on, rows
-// or none (fold_mark); with anything to do (`any`), launch(c->stream) runs between
+// The fold's place on the context's main stream: the launch counts as folded from here on,
+// rows or none (fold_mark); with anything to do (`any`), launch(main stream) runs between
 // fold_enter and fold_leave.  The caller bumps its counters when this returns OLPE_OK.
 template <class Launch>
 int fold_run(FoldBase *b, const olpe_ctx *c, bool any, Launch launch) {
@@ -140,7 +144,7 @@ int fold_run(FoldBase *b, const olpe_ctx *c, bool any, Launch launch) {
   if (!any) return OLPE_OK;
   int rc;
   if ((rc = fold_enter(b, c))) return rc;
-  if ((rc = launch(c->stream))) return rc;
+  if ((rc = launch(main_stream(c)))) return rc;
   return fold_leave(b, c);
 }
 

@@ -13,10 +13,38 @@ struct olpe_ctx {
   int eval_mode = 1;   // OLPE_EVAL_FAST (default) / OLPE_EVAL_EXACT
   bool lds_img = true; // cutout + 1/err staged in LDS by the sampler
   int wpb = 0;         // waves per workgroup of the 64x64 LDS sampler (0 = 12)
+  // the main-class stream.  Only olpe_main() (below) hands it out: everything but the
+  // sampler launches and the moments fold runs on it, behind all of them
   hipStream_t stream = nullptr;
-  // start/stop events of the last kRing sampler launches (olpe_kernel_times)
+  // Launch overlap (olpe_run).  Sampler launches alternate between two
+  // streams by parity, so that launch k+1 can take the CUs launch k's tail frees; each
+  // parity has its own queue counter (d_queue[0] / [5]) and base, hold word and chain
+  // buffer.  The moments fold of a launch runs on that launch's stream.
+  hipStream_t sstream[2] = {nullptr, nullptr};
+  int par = 0;                       // parity of the last sampler launch
+  hipEvent_t ev_tail[2] = {};        // the last work enqueued on sstream[p]
+  hipEvent_t ev_fold = nullptr;      // end of the last moments fold
+  hipEvent_t ev_main = nullptr;      // the main-class work a launch or fold must follow
+  bool pend = false;                 // sampler-stream work the main stream has not waited on
+  bool main_dirty = false;           // main-class work enqueued since the last launch
+  bool overlap_on = true;            // OLPE_OVERLAP
+  bool prev_queue = false;           // the last launch ran the unit queue ...
+  long long prev_W = 0;              // ... over this many walkers ...
+  unsigned prev_tag = 0;             // ... and its last chunks publish this tag
+  unsigned long long *prev_qptr = nullptr;   // its queue counter and that counter's base
+  unsigned long long prev_qbase = 0;         // (the gate in front of an overlapped launch)
+  int prev_slot = -1;                // its slot in ev[] (-1: no launch to follow)
+  long long overlaps = 0;            // launches that overlapped (olpe_test_overlaps)
+  unsigned long long qbase2[2] = {0, 0};
+  double *d_chain2[2] = {nullptr, nullptr};
+  size_t chain_cap2[2] = {0, 0};
+  // start/stop events of the last kRing sampler launches (olpe_kernel_times), one slot
+  // more so that the oldest one's predecessor is still there; ev_ovl: the launch
+  // overlapped its predecessor, whose end event then bounds its time from below
   static constexpr int kRing = 64;
-  hipEvent_t ev[kRing][2] = {};
+  static constexpr int kSlots = kRing + 1;
+  hipEvent_t ev[kSlots][2] = {};
+  bool ev_ovl[kSlots] = {};
   long long launches = 0;
   double2 *d_DE = nullptr;   // [n*n] {data as f64, 1/err}, {0,0} where masked (EXACT)
   double2 *d_DW = nullptr;   // [n*n] {data/err, 1/err}, {0,0} where masked (FAST)
@@ -32,7 +60,7 @@ struct olpe_ctx {
   double *d_gauss = nullptr;     // [W]
   int *d_hasg = nullptr;         // [W]
   long long *d_done = nullptr;   // [W]
-  // last launch's chain / trace
+  // last launch's chain / trace (d_chain, chain_cap: d_chain2 / chain_cap2 [par])
   double *d_chain = nullptr;
   size_t chain_cap = 0;
   long long chain_rows = 0;
@@ -43,10 +71,10 @@ struct olpe_ctx {
   // scratch for olpe_model / olpe_chi2_batch
   double *d_scratch = nullptr, *d_scratch2 = nullptr;
   size_t scratch_cap = 0, scratch2_cap = 0;
-  // walker queue of the sampler (one 64-bit counter; each launch takes W + its waves
-  // from it, so no reset between launches): qbase = the counter's value at launch
+  // walker queue of the sampler (one 64-bit counter per launch parity; each launch takes
+  // W + its waves from its own, so no reset between launches): qbase2[p] = that
+  // counter's value at launch
   unsigned long long *d_queue = nullptr;
-  unsigned long long qbase = 0;
   bool queue_on = true;
   int n_cu = 0;
   // work units (choose_units): walkers cut into chunks handed between waves through
@@ -109,6 +137,15 @@ int set_err(int code, const char *fmt, ...);
     if (e_ != hipSuccess)                                                               \
       return ::olpe::set_err(OLPE_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
+// The main-class stream: first makes it wait for every sampler launch and moments fold
+// still outstanding on the sampler streams, and notes that the next launch has to follow
+// what the caller enqueues (olpe.hip).  Every use of the context's stream outside
+// olpe_run and olpe_moments_accumulate goes through it.
+hipStream_t olpe_main(olpe_ctx *c);
+// the stream of the last sampler launch, for the moments fold: behind the previous fold
+// and any main-class work; olpe_fold_done records the fold's end
+int olpe_fold_stream(olpe_ctx *c, hipStream_t *s);
+int olpe_fold_done(olpe_ctx *c);
 void olpe_comm_release(olpe_ctx *c);
 // the default jump widths into c->d_widths (with_base: into c->d_wdef too), a launch on
 // the context's stream (olpe.hip, where the default tables live)

@@ -263,8 +263,8 @@ int olpe_moments_prepare(olpe_ctx *c) {
   int rc;
   if ((rc = ensure_moments(c))) return rc;
   if (c->mom_n == 0) {      // nothing folded yet: zero means / M2 (the sums are 0)
-    HIPCHK(hipMemsetAsync(c->d_mmean, 0, (size_t)c->W * c->ps * 8, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_mm2, 0, (size_t)c->W * c->ps * 8, c->stream));
+    HIPCHK(hipMemsetAsync(c->d_mmean, 0, (size_t)c->W * c->ps * 8, olpe_main(c)));
+    HIPCHK(hipMemsetAsync(c->d_mm2, 0, (size_t)c->W * c->ps * 8, olpe_main(c)));
   }
   return OLPE_OK;
 }
@@ -279,13 +279,13 @@ int olpe_moments_local(olpe_ctx *c, const double *d_centre, double *d_out) {
   const size_t cols = (size_t)3 * c->ps + 2 * c->np;
   if (!c->d_mpart || c->mpart_cap < cols * nblk || !c->d_mmean)
     return set_err(OLPE_ESTATE, "moments summary before its buffers were prepared");
-  hipLaunchKernelGGL(summary_stage1, dim3(nblk), dim3(kThreads), 0, c->stream, c->d_mmean,
+  hipLaunchKernelGGL(summary_stage1, dim3(nblk), dim3(kThreads), 0, olpe_main(c), c->d_mmean,
                      c->d_mm2, d_centre, c->d_tries, c->d_acc, (long long)c->W, c->ps, c->np,
                      nblk, c->d_mpart);
   HIPCHK(hipGetLastError());
   // one block per output column, the blocks' partials in a fixed order
   hipLaunchKernelGGL(olpe::reduce_stage2_kernel<kThreads>, dim3((unsigned)cols), dim3(kThreads),
-                     0, c->stream, c->d_mpart, nblk, d_out + 2);
+                     0, olpe_main(c), c->d_mpart, nblk, d_out + 2);
   HIPCHK(hipGetLastError());
   return OLPE_OK;
 }
@@ -309,17 +309,23 @@ int olpe_moments_accumulate(olpe_ctx *c) {
   c->mom_folded = c->launches;
   const long long nrec = c->chain_rows;
   if (nrec == 0) return OLPE_OK;
+  // the fold class of DESIGN.md §3: on the stream of the launch whose rows it reads,
+  // behind the previous fold (both update the same running pair), so that the other
+  // parity's launch does not wait for it
+  hipStream_t s = nullptr;
+  if ((rc = olpe_fold_stream(c, &s))) return rc;
   if (nrec >= kFoldRowsMin && c->ps <= 64) {
     hipLaunchKernelGGL(fold_rows_kernel, dim3((unsigned)((c->W + kFoldWaves - 1) / kFoldWaves)),
-                       dim3(64 * kFoldWaves), 0, c->stream, c->d_chain, (long long)c->W, c->ps,
+                       dim3(64 * kFoldWaves), 0, s, c->d_chain, (long long)c->W, c->ps,
                        nrec, (double)c->mom_n, c->d_mmean, c->d_mm2);
   } else {
     const long long total = (long long)c->W * c->ps;
     hipLaunchKernelGGL(fold_cols_kernel, dim3((unsigned)((total + kThreads - 1) / kThreads)),
-                       dim3(kThreads), 0, c->stream, c->d_chain, (long long)c->W, c->ps, nrec,
+                       dim3(kThreads), 0, s, c->d_chain, (long long)c->W, c->ps, nrec,
                        (double)c->mom_n, c->d_mmean, c->d_mm2);
   }
   HIPCHK(hipGetLastError());
+  if ((rc = olpe_fold_done(c))) return rc;
   c->mom_n += nrec;
   return OLPE_OK;
 }
@@ -335,7 +341,7 @@ int olpe_moments_get(olpe_ctx *c, long long *n, double *mean, double *m2) {
   if (!c || !n) return set_err(OLPE_EINVAL, "NULL argument");
   if (!c->d_state) return set_err(OLPE_ESTATE, "no ensemble");
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(olpe_main(c)));
   *n = c->mom_n;
   const size_t m = (size_t)c->W * c->ps;
   std::vector<double> t(m, 0.0);
@@ -358,7 +364,7 @@ int olpe_moments_set(olpe_ctx *c, long long n, const double *mean, const double 
   if (!c || n < 0 || (n > 0 && (!mean || !m2))) return set_err(OLPE_EINVAL, "bad argument");
   if (!c->d_state) return set_err(OLPE_ESTATE, "call olpe_seed first");
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(olpe_main(c)));
   int rc;
   if ((rc = ensure_moments(c))) return rc;
   const size_t m = (size_t)c->W * c->ps;
@@ -388,13 +394,13 @@ int olpe_moments_summary(olpe_ctx *c, const double *centre, double *out) {
   hipError_t e = hipSuccess;
   if (centre) {
     dc = d + len;
-    e = hipMemcpyAsync(dc, centre, c->ps * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    e = hipMemcpyAsync(dc, centre, c->ps * sizeof(double), hipMemcpyHostToDevice, olpe_main(c));
   }
   int rc = e == hipSuccess ? olpe_moments_prepare(c) : OLPE_OK;
   if (e == hipSuccess && rc == OLPE_OK) rc = olpe_moments_local(c, dc, d);
   if (e == hipSuccess && rc == OLPE_OK)
-    e = hipMemcpyAsync(out, d, len * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess && rc == OLPE_OK) e = hipStreamSynchronize(c->stream);
+    e = hipMemcpyAsync(out, d, len * sizeof(double), hipMemcpyDeviceToHost, olpe_main(c));
+  if (e == hipSuccess && rc == OLPE_OK) e = hipStreamSynchronize(olpe_main(c));
   (void)hipFree(d);
   if (rc) return rc;
   if (e != hipSuccess) return set_err(OLPE_EHIP, "moments summary: %s", hipGetErrorString(e));

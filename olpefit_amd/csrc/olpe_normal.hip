@@ -348,25 +348,25 @@ int olpe_normal_batch(olpe_ctx *c, const double *params, int W, double *chi2, do
   const size_t P = (size_t)c->np, nw = (size_t)W;
   const size_t pin = nw * c->ps, pout = nw * (1 + P + P * P);
   int rc;
-  HIPCHK(hipStreamSynchronize(c->stream));     // nothing in flight reads a buffer that grows
+  HIPCHK(hipStreamSynchronize(olpe_main(c)));     // nothing in flight reads a buffer that grows
   if ((rc = reserve(c, pin, pout))) return rc;
-  HIPCHK(hipMemcpyAsync(c->d_scratch, params, pin * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->d_scratch, params, pin * 8, hipMemcpyHostToDevice, olpe_main(c)));
   double *d_chi = c->d_scratch2, *d_grad = d_chi + nw, *d_jtj = d_grad + nw * P;
   const dim3 grid((unsigned)((nw + kWaves - 1) / kWaves)), block(kWaves * 64);
   if (c->nsrc == 2)
-    hipLaunchKernelGGL((normal_kernel<2>), grid, block, 0, c->stream, c->d_DE, c->n,
+    hipLaunchKernelGGL((normal_kernel<2>), grid, block, 0, olpe_main(c), c->d_DE, c->n,
                        c->bkgd_mode, c->d_scratch, W, d_chi, d_grad, d_jtj);
   else if (corner_mfma)
-    hipLaunchKernelGGL((normal_kernel<3, true>), grid, block, 0, c->stream, c->d_DE, c->n,
+    hipLaunchKernelGGL((normal_kernel<3, true>), grid, block, 0, olpe_main(c), c->d_DE, c->n,
                        c->bkgd_mode, c->d_scratch, W, d_chi, d_grad, d_jtj);
   else
-    hipLaunchKernelGGL((normal_kernel<3>), grid, block, 0, c->stream, c->d_DE, c->n,
+    hipLaunchKernelGGL((normal_kernel<3>), grid, block, 0, olpe_main(c), c->d_DE, c->n,
                        c->bkgd_mode, c->d_scratch, W, d_chi, d_grad, d_jtj);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(chi2, d_chi, nw * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(grad, d_grad, nw * P * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(jtj, d_jtj, nw * P * P * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(chi2, d_chi, nw * 8, hipMemcpyDeviceToHost, olpe_main(c)));
+  HIPCHK(hipMemcpyAsync(grad, d_grad, nw * P * 8, hipMemcpyDeviceToHost, olpe_main(c)));
+  HIPCHK(hipMemcpyAsync(jtj, d_jtj, nw * P * P * 8, hipMemcpyDeviceToHost, olpe_main(c)));
+  HIPCHK(hipStreamSynchronize(olpe_main(c)));
   return OLPE_OK;
 }
 
@@ -375,19 +375,19 @@ int olpe_test_jacobian(olpe_ctx *c, const double *vec, double *planes) {
   HIPCHK(hipSetDevice(c->device));
   const size_t npix = (size_t)c->n * c->n, pout = (size_t)c->np * npix;
   int rc;
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(olpe_main(c)));
   if ((rc = reserve(c, (size_t)c->ps, pout))) return rc;
-  HIPCHK(hipMemcpyAsync(c->d_scratch, vec, (size_t)c->ps * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->d_scratch, vec, (size_t)c->ps * 8, hipMemcpyHostToDevice, olpe_main(c)));
   const dim3 grid((unsigned)((npix + kThreads - 1) / kThreads)), block(kThreads);
   if (c->nsrc == 2)
-    hipLaunchKernelGGL((jacobian_kernel<2>), grid, block, 0, c->stream, c->d_scratch, c->n,
+    hipLaunchKernelGGL((jacobian_kernel<2>), grid, block, 0, olpe_main(c), c->d_scratch, c->n,
                        c->bkgd_mode, c->d_scratch2);
   else
-    hipLaunchKernelGGL((jacobian_kernel<3>), grid, block, 0, c->stream, c->d_scratch, c->n,
+    hipLaunchKernelGGL((jacobian_kernel<3>), grid, block, 0, olpe_main(c), c->d_scratch, c->n,
                        c->bkgd_mode, c->d_scratch2);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(planes, c->d_scratch2, pout * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(planes, c->d_scratch2, pout * 8, hipMemcpyDeviceToHost, olpe_main(c)));
+  HIPCHK(hipStreamSynchronize(olpe_main(c)));
   return OLPE_OK;
 }
 

@@ -383,7 +383,7 @@ int olpe_resid_create(olpe_ctx *c, const double *pivot, olpe_resid **out) {
   if (!rc) rc = alloc((void **)&r->d_planes, OLPE_RESID_PLANES * npix * 8, "the planes");
   if (!rc) rc = alloc(&r->d_fin, finblocks * sizeof(FinPart), "the finalize partials");
   // the cutout behind whatever the context's stream still has in flight
-  if (!rc && (hipStreamSynchronize(c->stream) != hipSuccess ||
+  if (!rc && (hipStreamSynchronize(olpe_main(c)) != hipSuccess ||
               hipMemcpy(r->d_DE, c->d_DE, npix * sizeof(double2), hipMemcpyDeviceToDevice) != hipSuccess ||
               hipMemset(r->d_sum, 0, 2 * npix * 8) != hipSuccess ||
               hipMemset(r->d_pivimg, 0, npix * 8) != hipSuccess ||

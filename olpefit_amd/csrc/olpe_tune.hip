@@ -114,14 +114,14 @@ __global__ void tune_update_kernel(int np, TuneBuf *b, double *w, const double *
 
 // the sums of the counters as they are when the stream gets here, into b->now
 int enqueue_sums(olpe_ctx *c, TuneBuf *b) {
-  HIPCHK(hipMemsetAsync(b->now, 0, sizeof(b->now), c->stream));
+  HIPCHK(hipMemsetAsync(b->now, 0, sizeof(b->now), olpe_main(c)));
   const unsigned blocks =
       (unsigned)std::min<long long>(((long long)c->W + kThreads - 1) / kThreads, kMaxBlocks);
   if (c->np == 16)
-    hipLaunchKernelGGL(tune_sum_kernel<16>, dim3(blocks), dim3(kThreads), 0, c->stream, c->d_tries,
+    hipLaunchKernelGGL(tune_sum_kernel<16>, dim3(blocks), dim3(kThreads), 0, olpe_main(c), c->d_tries,
                        c->d_acc, (long long)c->W, b->now);
   else
-    hipLaunchKernelGGL(tune_sum_kernel<19>, dim3(blocks), dim3(kThreads), 0, c->stream, c->d_tries,
+    hipLaunchKernelGGL(tune_sum_kernel<19>, dim3(blocks), dim3(kThreads), 0, olpe_main(c), c->d_tries,
                        c->d_acc, (long long)c->W, b->now);
   HIPCHK(hipGetLastError());
   return OLPE_OK;
@@ -144,7 +144,7 @@ int olpe_widths_set(olpe_ctx *c, const double *w) {
   }
   WidthsArg a = {};
   for (int j = 0; j < c->np; ++j) a.w[j] = w[j];
-  hipLaunchKernelGGL(widths_set_kernel, dim3(1), dim3(64), 0, c->stream, c->np, a, c->d_widths);
+  hipLaunchKernelGGL(widths_set_kernel, dim3(1), dim3(64), 0, olpe_main(c), c->np, a, c->d_widths);
   HIPCHK(hipGetLastError());
   return OLPE_OK;
 }
@@ -152,8 +152,8 @@ int olpe_widths_set(olpe_ctx *c, const double *w) {
 int olpe_widths_get(olpe_ctx *c, double *out) {
   if (!c || !out) return set_err(OLPE_EINVAL, "NULL argument");
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipMemcpyAsync(out, c->d_widths, (size_t)c->np * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(out, c->d_widths, (size_t)c->np * 8, hipMemcpyDeviceToHost, olpe_main(c)));
+  HIPCHK(hipStreamSynchronize(olpe_main(c)));
   return OLPE_OK;
 }
 
@@ -176,7 +176,7 @@ int olpe_tune_begin(olpe_ctx *c, double target, double gain) {
   c->tune_on = false;
   int rc;
   if ((rc = enqueue_sums(c, b))) return rc;
-  hipLaunchKernelGGL(tune_update_kernel, dim3(1), dim3(64), 0, c->stream, c->np, b, c->d_widths,
+  hipLaunchKernelGGL(tune_update_kernel, dim3(1), dim3(64), 0, olpe_main(c), c->np, b, c->d_widths,
                      c->d_wdef, 0.0, target, (TuneRec *)nullptr);
   HIPCHK(hipGetLastError());
   c->tune_on = true;
@@ -198,7 +198,7 @@ int olpe_tune_step(olpe_ctx *c) {
   if ((rc = enqueue_sums(c, b))) return rc;
   const int k = c->tune_k + 1;
   const double g = c->tune_gain / sqrt((double)k);
-  hipLaunchKernelGGL(tune_update_kernel, dim3(1), dim3(64), 0, c->stream, c->np, b, c->d_widths,
+  hipLaunchKernelGGL(tune_update_kernel, dim3(1), dim3(64), 0, olpe_main(c), c->np, b, c->d_widths,
                      c->d_wdef, g, c->tune_target, b->log + (k - 1));
   HIPCHK(hipGetLastError());
   c->tune_k = k;
@@ -209,7 +209,7 @@ int olpe_tune_get(olpe_ctx *c, int *steps, long long *dT, long long *dA, double 
   if (!c || !steps) return set_err(OLPE_EINVAL, "NULL argument");
   if (!c->d_tune) return set_err(OLPE_ESTATE, "no tuning session yet");
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(olpe_main(c)));
   const int k = c->tune_k;
   *steps = k;
   if (!k || (!dT && !dA && !widths)) return OLPE_OK;
