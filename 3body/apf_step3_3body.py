@@ -5,7 +5,8 @@ plot's histograms and quantile brackets, with --residuals the posterior's model 
 residual images, with --autocorr the chains' autocorrelation times and effective sample
 sizes, and with --photometry the companions' flux ratios and delta magnitudes, the FWHM and
 the sources' S/N, and with --covariance the parameter covariance, the error ellipses of b
-and c about a, the conditional widths and the multivariate Gelman-Rubin statistic; see
+and c about a, the conditional widths and the multivariate Gelman-Rubin statistic, and with
+--detect the companion detection map, its candidates and the contrast curve; see
 olpefit_amd/step3.py).
 
     python 3body/apf_step3_3body.py <image> <system> -s <walkers> [-a <burn>]
@@ -15,6 +16,8 @@ olpefit_amd/step3.py).
         [--autocorr [--autocorr-max-lag N] [--autocorr-c X]]
         [--photometry [--photometry-thin N]]
         [--covariance [--covariance-thin N]]
+        [--detect [--detect-thin N] [--detect-oversample 1|2|4] [--detect-threshold X]
+                  [--detect-k K]]
 """
 import os
 import sys

@@ -13,7 +13,10 @@ FWHM numbers, written to <frame>_photometry.npz and, with --astrometry, into the
 fields of the epoch_grand_pasep line; with --covariance the parameter covariance and
 correlations, the companion's error ellipse, the conditional widths and the multivariate
 Gelman-Rubin statistic, the cross-column sums folded on the GPU and written to
-<frame>_covariance.npz (nothing is drawn).
+<frame>_covariance.npz; with --detect the companion detection map (the matched filter of every
+folded row's residual with its own PSF at every candidate position), its candidates and the
+contrast curve, folded on the GPU and written to <frame>_detect.npz and three FITS files
+(nothing is drawn).
 
     python apf_step3.py <dir>/N2.<date>.<frame>.LDIF.fits <system> -s <walkers> [-a <burn>]
         [--astrometry [--distortion X.fits Y.fits] [--delta-r MAS] [--prepost pre|post]]
@@ -22,6 +25,8 @@ Gelman-Rubin statistic, the cross-column sums folded on the GPU and written to
         [--autocorr [--autocorr-max-lag N] [--autocorr-c X]]
         [--photometry [--photometry-thin N]]
         [--covariance [--covariance-thin N]]
+        [--detect [--detect-thin N] [--detect-oversample 1|2|4] [--detect-threshold X]
+                  [--detect-k K]]
 """
 import os
 import sys

@@ -837,6 +837,80 @@ int olpe_cov_add(olpe_cov *h, int ncols, long long walkers, unsigned long long n
  * automatic one is forgotten; the launch folded last may be folded again. */
 int olpe_cov_reset(olpe_cov *h);
 
+/* --- companion detection map (apf_step2.py:78-124, :134-137) -----------------------------
+ * "Is there another source in this frame, and how faint a one would have been seen?"  At
+ * every candidate position c = (x_c, y_c) of the lattice x_c, y_c = j / oversample, j = 0 ..
+ * oversample (n - 1) (G = (oversample (n - 1) + 1)^2 candidates, row y_c major), the
+ * matched filter of a sample's residual with that sample's own unit PSF: with theta the
+ * sample, M its build_analytical_model (EXACT operation order, whatever the context's eval
+ * mode), err as apf_step2.py:210 (the 1 / err the context staged), pixels i,
+ *   psi(u, v) = (1 - q) g1(u, v) + q g2(u - dx, v - dy)          (apf_step2.py:78-103)
+ *   g_k(u, v) = exp(-((a_k u^2) + (b_k u) v + c_k v^2))          (narrow k = 1, wide k = 2)
+ *   z_i = w_i (D_i - M_i),  w_i = (1 / err_i)^2, 0 where masked,  K_i = psi(x_i - x_c, y_i - y_c)
+ *   N = sum_i z_i K_i,  Q = sum_i w_i K_i^2,  A = N / Q,  sigma_A = 1 / sqrt(Q),  snr = N / sqrt(Q)
+ * A is the maximum-likelihood amplitude of one more source of the shared shape, in the units
+ * of A_k - b.  It is a score test: the fitted sources stay at the sample's values, nothing
+ * is refitted, and near a fitted source A is degenerate with that source's amplitude.  A
+ * candidate no unmasked pixel sees (Q = 0) is NaN in every plane.  Folded over the samples
+ * are five planes [G] of sums shifted about the pivot vector's planes: sum (A - A_p),
+ * sum (A - A_p)^2, sum sigma_A^2, sum (snr - snr_p), sum (snr - snr_p)^2.  Counts, pivot,
+ * best row, unusable rows and additivity follow olpe_resid's rules.  No floating-point
+ * atomics: a candidate's sums take the same additions in the same order on any grid or CU
+ * count.  Calls on one object are not thread-safe.  Not covered: refitting with the extra
+ * source, a factorised (FAST) fold, a collective over the state, false-alarm calibration. */
+typedef struct olpe_detect olpe_detect;
+#define OLPE_DETECT_SUMS 5
+#define OLPE_DETECT_PLANES 10
+/* olpe_detect_finalize's planes [OLPE_DETECT_PLANES][G], over the folded samples:
+ *   [0] mean of A        [1] its np.std (ddof 0)      [2] sqrt(mean sigma_A^2)
+ *   [3] sqrt(mean sigma_A^2 + var A): the law of total variance, the PSF posterior's scatter
+ *       counted                                        [4] mean of snr      [5] its std
+ *   [6] [0] / [3]        [7] A, [8] sigma_A, [9] snr of the best sample.  Its scalars: */
+#define OLPE_DETECT_SCALARS 8
+#define OLPE_DETECT_USED 0      /* samples folded (usable) */
+#define OLPE_DETECT_BAD 1       /* unusable rows met */
+#define OLPE_DETECT_PIXELS 2    /* unmasked pixels */
+#define OLPE_DETECT_BLIND 3     /* candidates with Q = 0 */
+#define OLPE_DETECT_MAX6 4      /* max of plane 6 ... */
+#define OLPE_DETECT_MAX6_AT 5   /* ... and its candidate (the lowest on a tie; -1: none) */
+#define OLPE_DETECT_MIN6 6      /* min of plane 6 */
+#define OLPE_DETECT_MED3 7      /* median of plane 3 over the candidates that are not NaN */
+/* Copies ctx's staged cutout (apf_step2.py:176-210: data, 1/err, mask) device to device and
+ * takes its side, sources, bkgd_mode and device; independent of ctx afterwards.  pivot: a
+ * parameter vector (its PS - 1 parameters are read, all finite), or NULL: the first usable
+ * row folded becomes the pivot.  OLPE_EINVAL for an oversample outside {1, 2, 4} and for a
+ * side above 128. */
+int olpe_detect_create(olpe_ctx *ctx, const double *pivot, int oversample, olpe_detect **out);
+/* Frees the object of apf_step2.py:78-124's map (waits for its folds in flight). */
+void olpe_detect_destroy(olpe_detect *d);
+/* The map of apf_step2.py:78-124 for rows 0, row_step, ... of walkers 0, walker_step, ... of
+ * ctx's last launch, read from its device chain in place, walker-major (async on the
+ * context's stream, no copy).  Once per launch: OLPE_ESTATE if this launch was folded
+ * already; OLPE_EINVAL for a context of another device, side, nsrc or bkgd_mode. */
+int olpe_detect_fold_ctx(olpe_detect *d, olpe_ctx *ctx, int row_step, int walker_step);
+/* The map of apf_step2.py:78-124 for host rows [nsamples][PS], uploaded in bounded pieces. */
+int olpe_detect_fold_rows(olpe_detect *d, const double *rows, long long nsamples);
+/* The state (apf_step2.py:78-124 summed): samples used, unusable rows, pivot [PS], the sums
+ * [OLPE_DETECT_SUMS][G], best row [PS]; any may be NULL; pivot / best are NaN while there is
+ * none.  Waits for the folds in flight. */
+int olpe_detect_get(olpe_detect *d, long long *n, long long *n_bad, double *pivot, double *sums,
+                    double *best);
+/* Adds another object's, rank's or checkpoint's state (apf_step2.py:78-124 over the union of
+ * their rows).  OLPE_EINVAL if the pivots' parameters differ in any bit, unless this object
+ * holds no sample yet: it then adopts the incoming pivot.  This object's rows count as
+ * folded first: the incoming best row wins only with a strictly smaller chi^2. */
+int olpe_detect_add(olpe_detect *d, long long n, long long n_bad, const double *pivot,
+                    const double *sums, const double *best);
+/* Empties the state (apf_step2.py:78-124 starts over); a pivot given at create stays. */
+int olpe_detect_reset(olpe_detect *d);
+/* A, sigma_A and snr [3][G] of one explicit vector (apf_step2.py:78-124 at its PS - 1
+ * parameters, all finite); the state is left as it is. */
+int olpe_detect_point(olpe_detect *d, const double *vec, double *planes);
+/* The planes and scalars above (apf_step2.py:78-137 per plane) from the state, which it
+ * leaves as it is: more folds and another finalize may follow.  OLPE_ESTATE with no usable
+ * sample, or when no usable sample's chi^2 is a number. */
+int olpe_detect_finalize(olpe_detect *d, double *planes, double *scalars);
+
 #ifdef __cplusplus
 }
 #endif

@@ -153,6 +153,15 @@ SIGNATURES = {
     "olpe_cov_add": (_i, [_P, _i, _ll, C.c_ulonglong, C.c_ulonglong, _pd, _pd, _pd, _pu64,
                           _pd]),
     "olpe_cov_reset": (_i, [_P]),
+    "olpe_detect_create": (_i, [_P, _pd, _i, C.POINTER(_P)]),
+    "olpe_detect_destroy": (None, [_P]),
+    "olpe_detect_fold_ctx": (_i, [_P, _P, _i, _i]),
+    "olpe_detect_fold_rows": (_i, [_P, _pd, _ll]),
+    "olpe_detect_get": (_i, [_P, _pll, _pll, _pd, _pd, _pd]),
+    "olpe_detect_add": (_i, [_P, _ll, _ll, _pd, _pd, _pd]),
+    "olpe_detect_reset": (_i, [_P]),
+    "olpe_detect_point": (_i, [_P, _pd, _pd]),
+    "olpe_detect_finalize": (_i, [_P, _pd, _pd]),
     "olpe_moments_fault": (_i, [_P, _i]),
     "olpe_test_hold_handoff": (_i, [_P, _i]),
     "olpe_test_overlaps": (_i, [_P, _pll]),

@@ -47,6 +47,9 @@ def _get_sec(time_str):                     # apf_step3.py:318-320
     return float(h) * 3600 + float(m) * 60 + float(s)
 
 
+PIXSCALE = {"pre": 9.952, "post": 9.971}    # mas / px, apf_step3.py:224, :231
+
+
 def header_scalars(hdr, prepost: str) -> dict:
     """The host-side scalar work of apf_step3.py:218-231 and :294-337 (3body :336-380) and
     PARANTEL (:393): pixscale, rotation_angle, the vertical-angle-mode correction."""
@@ -54,10 +57,10 @@ def header_scalars(hdr, prepost: str) -> dict:
         raise ValueError("prepost must be 'pre' or 'post'")
     p, r, i, e = hdr['PARANG'], hdr['ROTPPOSN'], hdr['INSTANGL'], hdr['EL']
     if prepost == "pre":
-        pixscale = 9.952                              # :224
+        pixscale = PIXSCALE["pre"]                    # :224
         rotation_angle = p + r - e - i - 0.252        # :300, Yelda 2010
     else:
-        pixscale = 9.971                              # :231
+        pixscale = PIXSCALE["post"]                   # :231
         rotation_angle = p + r - e - i - 0.262        # :302, Service 2016
     out = {"prepost": prepost, "pixscale": pixscale, "rotation_angle": float(rotation_angle),
            "vertical_angle_mode": "no", "rotcorr": 0.0, "use_rotcorr": False,

@@ -187,7 +187,8 @@ def main(argv=None, nsrc: int = 2):
     ``--photometry`` the flux ratio, delta magnitude, FWHM and S/N (``photometry``),
     ``--covariance`` the parameter covariance, the companions' error ellipses, the conditional
     widths and the multivariate Gelman-Rubin statistic (``covariance``), ``--waic`` every
-    pixel's posterior deviance, WAIC and DIC (``waic``)."""
+    pixel's posterior deviance, WAIC and DIC (``waic``), ``--detect`` the companion detection
+    map, its candidates and the contrast curve (``detect``)."""
     import argparse
     import json
     import sys
@@ -266,6 +267,20 @@ def main(argv=None, nsrc: int = 2):
     ap.add_argument("--widths-out", type=str, default=None, metavar="FILE",
                     help="with --covariance: write the proposal widths the fold implies "
                          "(covariance.proposal_widths) as a widths file for step 2's --widths")
+    ap.add_argument("--detect", action="store_true",
+                    help="companion detection map and contrast curve of the chains (GPU): the "
+                         "matched filter of every folded row's residual with its own PSF at "
+                         "every candidate position; writes <frame>_detect.npz and three FITS "
+                         "files")
+    ap.add_argument("--detect-thin", type=int, default=1, metavar="N",
+                    help="fold every N-th row after the burn-in (a row costs 2 G n^2 FMAs: "
+                         "thin generously)")
+    ap.add_argument("--detect-oversample", type=int, choices=(1, 2, 4), default=1,
+                    help="candidate positions per pixel and axis")
+    ap.add_argument("--detect-threshold", type=float, default=5.0, metavar="X",
+                    help="candidates are the local maxima of the S/N map at or above X")
+    ap.add_argument("--detect-k", type=float, default=5.0, metavar="K",
+                    help="the contrast curve is K sigma over the primary's flux")
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
     say = (lambda *a: None) if args.quiet else print
     ncor = int(np.int_(args.size))                                  # :76-77
@@ -288,6 +303,7 @@ def main(argv=None, nsrc: int = 2):
                       ("corner", "a histogram is not a moment"),
                       ("residuals", "moments are not samples"),
                       ("waic", "moments are not samples"),
+                      ("detect", "moments are not samples"),
                       ("autocorr", "moments hold no order"),
                       ("photometry", "a percentile is not a moment")):
         if args.from_moments and getattr(args, flag):
@@ -299,6 +315,8 @@ def main(argv=None, nsrc: int = 2):
         ap.error(f"--residuals-thin {args.residuals_thin}: must be >= 1")
     if args.waic_thin < 1:
         ap.error(f"--waic-thin {args.waic_thin}: must be >= 1")
+    if args.detect_thin < 1:
+        ap.error(f"--detect-thin {args.detect_thin}: must be >= 1")
     if args.waic_against and not args.waic:
         ap.error("--waic-against compares the --waic fold: give --waic")
     if args.photometry_thin < 1:
@@ -364,6 +382,8 @@ def main(argv=None, nsrc: int = 2):
         out["covariance"] = covariance(args, chains, nsrc, stats, input_directory, say)
     if args.waic:
         out["waic"] = waic(args, chains, nsrc, stats, input_directory, say)
+    if args.detect:
+        out["detect"] = detect(args, chains, nsrc, stats, input_directory, say)
     with open(input_directory + "step3_summary.json", "w") as f:
         json.dump(out, f, indent=1)
     return out
@@ -557,6 +577,65 @@ def waic(args, chains, nsrc, stats, input_directory, say=print):
     if cmp_ is not None:
         out["against"] = {k: (v if isinstance(v, str) else num(v)) for k, v in cmp_.items()}
     return out
+
+
+def detect(args, chains, nsrc, stats, input_directory, say=print):
+    """Is there another source in the frame, and how faint a one would have been seen?  Over
+    the chains [N, M, PS] already read, every ``--detect-thin``-th row's residual
+    (``build_analytical_model``, apf_step2.py:106-124; 3body :106-125) is matched-filtered
+    with that row's own unit PSF (apf_step2.py:78-103) at every candidate position on the GPU
+    (detect.Detect) on the frame as step 2 staged it (apf_step2.py:160-161, :176-210;
+    ``--bkgd-mode`` as ``--residuals``), about theta_hat, the column means just computed.
+    Prints the scalars, the candidates above ``--detect-threshold`` and the ``--detect-k``
+    sigma contrast curve; writes ``<frame>_detect.npz`` and ``<frame>_snr.fits``,
+    ``_sigma.fits``, ``_contrast.fits`` beside the chain files and returns what
+    ``step3_summary.json`` records."""
+    from . import astrometry as am, detect as dt, fitsio
+    from .core import Sampler
+    labels = NAMES_2 if nsrc == 2 else NAMES_3
+    image, hdr = fitsio.getdata_header(args.image)
+    pixscale = am.PIXSCALE[resolve_prepost(args)]    # the scale alone: no pointing cards needed
+    say('Folding the companion detection map...')
+    prefix = results_prefix(args, input_directory)
+    theta_hat = np.array([stats[k]["mean"] for k in labels[:-1]])
+    if not np.isfinite(theta_hat).all():
+        raise ValueError("a column mean is not finite: --detect needs an additional_burnin "
+                         "that drops the NaN seed row")
+    os_ = args.detect_oversample
+    flux0, known = dt.flux0_of(theta_hat, nsrc), dt.known_of(theta_hat, nsrc)
+    with Sampler(image, hdr["ITIME"], hdr["COADDS"], hdr["MULTISAM"], hdr["SAMPMODE"],
+                 nsrc=nsrc, bkgd_mode=args.bkgd_mode) as s, \
+            dt.Detect(s, pivot=theta_hat, oversample=os_) as d:
+        d.fold_rows(chains[::args.detect_thin])
+        img, scal = d.finalize()
+        img, scal = dict(zip(dt.PLANES, img)), d._scalars(scal)
+        curve = dt.contrast_curve(img["sigma_total"], known[0], flux0, pixscale,
+                                  k=args.detect_k, oversample=os_)
+        cands = dt.candidates(img["snr_marg"], img["amp_mean"], img["sigma_total"], known,
+                              threshold=args.detect_threshold,
+                              exclude_px=dt.default_exclude_px(theta_hat, nsrc),
+                              oversample=os_, flux0=flux0, pixscale=pixscale)
+        keys = ("x", "y", "snr", "amp", "sigma", "contrast", "dmag", "sep_px", "pa_deg")
+        d.save(prefix + "_detect.npz", thin=np.int64(args.detect_thin),
+               bkgd_mode=np.int64(args.bkgd_mode), theta_hat=theta_hat,
+               flux0=np.float64(flux0), pixscale=np.float64(pixscale),
+               k=np.float64(args.detect_k), threshold=np.float64(args.detect_threshold),
+               candidates=np.array([[c[k] for k in keys] for c in cands]).reshape(-1, len(keys)),
+               candidates_flagged=np.array([c["flagged"] for c in cands], dtype=bool),
+               **{"curve_" + k: v for k, v in curve.items()})
+        files = d.write_fits(prefix, flux0=flux0, k=args.detect_k)
+    for line in dt.table_lines(scal, cands, curve):
+        say(line)
+
+    def num(v):                                   # JSON has no NaN
+        if isinstance(v, (bool, int, str)):
+            return v
+        return float(v) if np.isfinite(v) else None
+    return {"file": prefix + "_detect.npz", "fits": files, "thin": args.detect_thin,
+            "oversample": os_, "bkgd_mode": args.bkgd_mode, "threshold": args.detect_threshold,
+            "k": args.detect_k, "flux0": num(flux0), **{k: num(v) for k, v in scal.items()},
+            "candidates": [{k: num(v) for k, v in c.items()} for c in cands],
+            "curve": {k: [num(x) for x in np.asarray(v).tolist()] for k, v in curve.items()}}
 
 
 def resolve_prepost(args):
