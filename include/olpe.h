@@ -857,7 +857,7 @@ int olpe_cov_reset(olpe_cov *h);
  * best row, unusable rows and additivity follow olpe_resid's rules.  No floating-point
  * atomics: a candidate's sums take the same additions in the same order on any grid or CU
  * count.  Calls on one object are not thread-safe.  Not covered: refitting with the extra
- * source, a factorised (FAST) fold, a collective over the state, false-alarm calibration. */
+ * source, a factorised (FAST) fold, a collective over the state. */
 typedef struct olpe_detect olpe_detect;
 #define OLPE_DETECT_SUMS 5
 #define OLPE_DETECT_PLANES 10
@@ -910,6 +910,61 @@ int olpe_detect_point(olpe_detect *d, const double *vec, double *planes);
  * leaves as it is: more folds and another finalize may follow.  OLPE_ESTATE with no usable
  * sample, or when no usable sample's chi^2 is a number. */
 int olpe_detect_finalize(olpe_detect *d, double *planes, double *scalars);
+
+/* --- false-alarm calibration of the detection map (apf_step2.py:78-124, :210) -------------
+ * "What does a 5 sigma candidate of this map mean?"  A candidate's snr is standard normal
+ * under the noise model, a map is up to 259,081 strongly correlated candidates: what counts is
+ * the distribution of the map's maximum with no further source in the frame.  theta is one
+ * parameter vector; K_i(c), w_i, Q(c) are the map's at theta.  Realisation r, r = 0, 1, ...:
+ *   eps_r = np.random.RandomState((seed + r) mod 2^32).standard_normal(n n) in raster order
+ *           (MT19937, the legacy polar method); every pixel takes a draw, masked or not
+ *   y_r,i = eps_r,i (1 / err_i), 0 at masked pixels (the 1 / err the context staged)
+ *   snr_r(c) = scale(c) ((sum_i K_i(c) y_r,i) / sqrt(Q(c))), NaN where Q(c) = 0
+ * Each map is reduced on the device; NaN candidates are left out everywhere:
+ *   max_all, argmax_all  the maximum and its candidate (row * g + column; the first on a tie;
+ *                        NaN and -1 with no candidate)
+ *   max_out, argmax_out  the same over the candidates farther than exclude_px from every
+ *                        known source (detect.py's flag)
+ *   peaks_all, peaks_out the strict local maxima at or above the threshold over the 8 lattice
+ *                        neighbours, a NaN neighbour counting as none (a plateau has none)
+ *   ring_max [nring]     the maximum of ring k = floor(hypot(x - cx, y - cy) / bin_px), NaN
+ *                        for a ring without a candidate; nring = the largest ring + 1
+ * The order of a candidate's additions depends on the frame's shape only, never on the batch
+ * size, the number of realisations or the position in a batch; no floating-point atomics.
+ * The fit is not redone per realisation.  Calls on one object are not thread-safe. */
+typedef struct olpe_detect_null olpe_detect_null;
+/* Evaluates d at vec (its PS - 1 parameters, all finite) and copies the tables, Q and the
+ * staged cutout (apf_step2.py:78-103, :210): independent of d afterwards.  scale [G] finite
+ * and > 0, or NULL for 1; known [nknown][2] the fitted sources' (x, y); centre [2];
+ * batch: realisations per batch, 0 = from a byte budget (any value gives the same bits).
+ * Arguments are checked before any GPU call. */
+int olpe_detect_null_create(olpe_detect *d, const double *vec, const double *scale,
+                            const double *known, int nknown, double exclude_px,
+                            const double *centre, double bin_px, double threshold,
+                            unsigned long long seed, int batch, olpe_detect_null **out);
+/* Frees the object of apf_step2.py:78-124's null maps. */
+void olpe_detect_null_destroy(olpe_detect_null *h);
+/* count more realisations of apf_step2.py:78-124's map under the noise of :210, generated
+ * on the device, continuing at realisation index `done`.  OLPE_ESTATE after
+ * olpe_detect_null_run_frames on the same object. */
+int olpe_detect_null_run(olpe_detect_null *h, long long count);
+/* count realisations of apf_step2.py:78-124's map from explicit host noise eps
+ * [count][n][n] in place of the generator.  OLPE_ESTATE after olpe_detect_null_run. */
+int olpe_detect_null_run_frames(olpe_detect_null *h, const double *eps, long long count);
+/* The reductions of apf_step2.py:78-124's null maps, per realisation so far: *done, *nring,
+ * then arrays [done] (ring_max [done][nring]); any may be NULL. */
+int olpe_detect_null_get(olpe_detect_null *h, long long *done, int *nring, double *max_all,
+                         long long *argmax_all, double *max_out, long long *argmax_out,
+                         long long *peaks_all, long long *peaks_out, double *ring_max);
+/* Recomputes apf_step2.py:78-124's snr maps [count][G] of the generated realisations r0 ..
+ * r0 + count - 1; the results so far are left as they are. */
+int olpe_detect_null_maps(olpe_detect_null *h, long long r0, long long count, double *out);
+/* The noise frames eps [count][n][n] (apf_step2.py:210's unit deviates) of the generated
+ * realisations r0 .. r0 + count - 1. */
+int olpe_detect_null_noise(olpe_detect_null *h, long long r0, long long count, double *out);
+/* Forgets the realisations (apf_step2.py:78-124 starts over at index 0, generated or
+ * explicit). */
+int olpe_detect_null_reset(olpe_detect_null *h);
 
 #ifdef __cplusplus
 }

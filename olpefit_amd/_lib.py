@@ -162,6 +162,16 @@ SIGNATURES = {
     "olpe_detect_reset": (_i, [_P]),
     "olpe_detect_point": (_i, [_P, _pd, _pd]),
     "olpe_detect_finalize": (_i, [_P, _pd, _pd]),
+    "olpe_detect_null_create": (_i, [_P, _pd, _pd, _pd, _i, _d, _pd, _d, _d, C.c_ulonglong, _i,
+                                     C.POINTER(_P)]),
+    "olpe_detect_null_destroy": (None, [_P]),
+    "olpe_detect_null_run": (_i, [_P, _ll]),
+    "olpe_detect_null_run_frames": (_i, [_P, _pd, _ll]),
+    "olpe_detect_null_get": (_i, [_P, _pll, C.POINTER(_i), _pd, _pll, _pd, _pll, _pll, _pll,
+                                  _pd]),
+    "olpe_detect_null_maps": (_i, [_P, _ll, _ll, _pd]),
+    "olpe_detect_null_noise": (_i, [_P, _ll, _ll, _pd]),
+    "olpe_detect_null_reset": (_i, [_P]),
     "olpe_moments_fault": (_i, [_P, _i]),
     "olpe_test_hold_handoff": (_i, [_P, _i]),
     "olpe_test_overlaps": (_i, [_P, _pll]),

@@ -16,7 +16,8 @@ SOURCES = [os.path.join(CSRC, f) for f in ("olpe.hip", "olpe_comm.hip", "olpe_mo
                                             "olpe_corner.hip", "olpe_resid.hip",
                                             "olpe_acf.hip", "olpe_phot.hip", "olpe_cov.hip",
                                             "olpe_tune.hip", "olpe_lik.hip",
-                                            "olpe_normal.hip", "olpe_detect.hip")]
+                                            "olpe_normal.hip", "olpe_detect.hip",
+                                            "olpe_detnull.hip")]
 DEPS = SOURCES + [os.path.join(CSRC, f) for f in ("olpe_device.h", "olpe_internal.h",
                                                  "olpe_fold.h", "olpe_select.h", "olpe_reduce.h",
                                                  "olpe_store.h", "olpe_samples.h",

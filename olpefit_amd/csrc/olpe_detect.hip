@@ -707,3 +707,20 @@ int olpe_detect_finalize(olpe_detect *d, double *planes, double *scalars) {
 }
 
 }  // extern "C"
+
+// olpe_internal.h: the hand-over to olpe_detnull.hip
+int olpe_detect_view_at(olpe_detect *d, const double *vec, olpe_detect_view *v) {
+  *v = olpe_detect_view{d->device, d->n, d->os, d->gs, d->ps, d->tabs, nullptr, nullptr, nullptr,
+                        nullptr};
+  if (!vec) return OLPE_OK;
+  HIPCHK(hipSetDevice(d->device));
+  int rc;
+  if ((rc = drain(d))) return rc;
+  HIPCHK(hipMemcpy(d->d_vec, vec, (size_t)(d->ps - 1) * 8, hipMemcpyHostToDevice));
+  if ((rc = eval_one(d, d->d_vec, d->d_out))) return rc;
+  v->tab = d->d_tab;
+  v->DE = d->d_DE;
+  v->Q = d->d_nq + d->G;
+  v->sigma = d->d_out + d->G;
+  return OLPE_OK;
+}

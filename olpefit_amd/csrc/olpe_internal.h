@@ -156,3 +156,19 @@ int olpe_comm_setup(olpe_ctx *c);
 // this context's walkers into d_out[2 ..], launches only
 int olpe_moments_prepare(olpe_ctx *c);
 int olpe_moments_local(olpe_ctx *c, const double *d_centre, double *d_out);
+// What olpe_detnull.hip takes from an olpe_detect (olpe_detect.hip; not part of the C-ABI):
+// its shape, and with a vector (host, PS - 1 parameters) that vector evaluated as
+// olpe_detect_point does, synchronously, the pointers then being the object's slot-0 tables
+// [os^2][2n - 1][2n - 1], its staged cutout [n^2], and the vector's Q [G] and sigma_A [G]
+// planes, valid until the object's next call.  vec NULL: the shape only, no GPU call.
+struct olpe_detect;
+struct olpe_detect_view {
+  int device, n, os, gs, ps;
+  size_t tabs;
+  const double *tab;
+  const double2 *DE;
+  const double *Q;
+  const double *sigma;
+};
+__attribute__((visibility("hidden"))) int olpe_detect_view_at(olpe_detect *d, const double *vec,
+                                                              olpe_detect_view *v);

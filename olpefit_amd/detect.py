@@ -23,8 +23,8 @@ which is why ``candidates`` flags (and keeps) what lies within ``exclude_px`` of
 The NumPy functions below (``planes_from_state``, ``contrast_curve``, ``candidates``,
 ``merge_states``, ``table_lines``) need no GPU.  Not covered: refitting with the extra source,
 a step-1 guess file for the 3-source scripts, sky-frame position angles, a collective over
-the state, a factorised (FAST) fold, ``--detect`` in step 2, false-alarm calibration.
-Nothing here imports matplotlib or the oracle.
+the state, a factorised (FAST) fold, ``--detect`` in step 2.  (What the threshold means over
+a map's correlated candidates: detect_null.)  Nothing here imports matplotlib or the oracle.
 """
 from __future__ import annotations
 

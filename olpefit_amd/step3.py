@@ -281,6 +281,15 @@ def main(argv=None, nsrc: int = 2):
                     help="candidates are the local maxima of the S/N map at or above X")
     ap.add_argument("--detect-k", type=float, default=5.0, metavar="K",
                     help="the contrast curve is K sigma over the primary's flux")
+    ap.add_argument("--detect-null", type=int, default=0, metavar="R",
+                    help="with --detect: calibrate the map's false-alarm rate on R noise "
+                         "realisations drawn and matched-filtered on the GPU at the column "
+                         "means; writes <frame>_detect_null.npz")
+    ap.add_argument("--detect-null-seed", type=int, default=0, metavar="S",
+                    help="realisation r draws from RandomState((S + r) mod 2^32)")
+    ap.add_argument("--detect-fap", type=float, default=0.01, metavar="P",
+                    help="the per-map (and per-ring) false-alarm probability the calibrated "
+                         "threshold and contrast curve are quoted for")
     args = ap.parse_args(sys.argv[1:] if argv is None else argv)
     say = (lambda *a: None) if args.quiet else print
     ncor = int(np.int_(args.size))                                  # :76-77
@@ -317,6 +326,13 @@ def main(argv=None, nsrc: int = 2):
         ap.error(f"--waic-thin {args.waic_thin}: must be >= 1")
     if args.detect_thin < 1:
         ap.error(f"--detect-thin {args.detect_thin}: must be >= 1")
+    if args.detect_null and not args.detect:
+        ap.error("--detect-null calibrates the --detect map: give --detect")
+    if args.detect_null < 0 or args.detect_null_seed < 0:
+        ap.error(f"--detect-null {args.detect_null}, --detect-null-seed "
+                 f"{args.detect_null_seed}: must be >= 0")
+    if not 0.0 < args.detect_fap < 1.0:
+        ap.error(f"--detect-fap {args.detect_fap}: between 0 and 1")
     if args.waic_against and not args.waic:
         ap.error("--waic-against compares the --waic fold: give --waic")
     if args.photometry_thin < 1:
@@ -624,18 +640,59 @@ def detect(args, chains, nsrc, stats, input_directory, say=print):
                candidates_flagged=np.array([c["flagged"] for c in cands], dtype=bool),
                **{"curve_" + k: v for k, v in curve.items()})
         files = d.write_fits(prefix, flux0=flux0, k=args.detect_k)
+        null = (detect_null(args, d, theta_hat, img, cands, curve, known, flux0, prefix)
+                if args.detect_null else None)
     for line in dt.table_lines(scal, cands, curve):
         say(line)
+    if null:
+        for line in null.pop("lines"):
+            say(line)
 
     def num(v):                                   # JSON has no NaN
         if isinstance(v, (bool, int, str)):
             return v
         return float(v) if np.isfinite(v) else None
-    return {"file": prefix + "_detect.npz", "fits": files, "thin": args.detect_thin,
-            "oversample": os_, "bkgd_mode": args.bkgd_mode, "threshold": args.detect_threshold,
-            "k": args.detect_k, "flux0": num(flux0), **{k: num(v) for k, v in scal.items()},
-            "candidates": [{k: num(v) for k, v in c.items()} for c in cands],
-            "curve": {k: [num(x) for x in np.asarray(v).tolist()] for k, v in curve.items()}}
+    out = {"file": prefix + "_detect.npz", "fits": files, "thin": args.detect_thin,
+           "oversample": os_, "bkgd_mode": args.bkgd_mode, "threshold": args.detect_threshold,
+           "k": args.detect_k, "flux0": num(flux0), **{k: num(v) for k, v in scal.items()},
+           "candidates": [{k: num(v) for k, v in c.items()} for c in cands],
+           "curve": {k: [num(x) for x in np.asarray(v).tolist()] for k, v in curve.items()}}
+    if null:
+        def clean(v):
+            if isinstance(v, (list, tuple)):
+                return [clean(x) for x in v]
+            return v if v is None else num(v)
+        out["detect_null"] = {k: clean(v) for k, v in null.items()}
+    return out
+
+
+def detect_null(args, d, theta_hat, img, cands, curve, known, flux0, prefix):
+    """What does ``--detect-threshold`` mean?  ``--detect-null`` R noise realisations of the
+    frame's own err (apf_step2.py:210) are drawn and matched-filtered on the GPU at theta_hat
+    (detect_null.DetectNull) with the denominator of ``snr_marg``, the map the candidates are
+    taken from: scale = sigma_A(theta_hat) / sigma_total.  Writes ``<frame>_detect_null.npz``
+    and returns the scalars ``step3_summary.json`` records, with the ``lines`` to print."""
+    from . import detect as dt, detect_null as dn
+    os_ = args.detect_oversample
+    with np.errstate(all="ignore"):
+        scale = d.point(theta_hat)[1] / img["sigma_total"]
+    scale = np.where(np.isfinite(scale) & (scale > 0.0), scale, 1.0)
+    ex = dt.default_exclude_px(theta_hat, d.nsrc)
+    with dn.DetectNull(d, theta_hat, scale=scale, known=known, exclude_px=ex, centre=known[0],
+                       threshold=args.detect_threshold, seed=args.detect_null_seed) as h:
+        h.run(args.detect_null)
+        res = h.results()
+    summ = dn.summarise(res, args.detect_threshold, args.detect_fap, cands=cands)
+    ring_k = dn.ring_thresholds(res["ring_max"], args.detect_fap)
+    cal = dn.calibrated_curve(curve, img["sigma_total"], ring_k, known[0], flux0, oversample=os_)
+    with open(prefix + "_detect_null.npz", "wb") as f:
+        np.savez(f, **{k: np.asarray(v) for k, v in res.items()}, scale=scale, ring_k=ring_k,
+                 fap=np.float64(args.detect_fap), seed=np.int64(args.detect_null_seed),
+                 **{"curve_" + k: cal[k] for k in ("k", "contrast_median_cal", "contrast_min_cal",
+                                                   "dmag_median_cal", "dmag_min_cal")})
+    return {"file": prefix + "_detect_null.npz", "seed": args.detect_null_seed, **summ,
+            "curve_k": cal["k"].tolist(), "curve_dmag_median_cal": cal["dmag_median_cal"].tolist(),
+            "lines": dn.table_lines(summ, cands, cal)}
 
 
 def resolve_prepost(args):

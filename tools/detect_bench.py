@@ -11,6 +11,18 @@ and the fastest time of each fold, the detection fold's FP64 rate from 2 G n^2 l
 sample and plane (N and Q: 4 G n^2 flop-pairs) as a fraction of the 2.4 GHz vector peak
 (256 CUs x 4 SIMDs x 16 lanes), the ratio to the residual fold, and the time of one sample's
 K @ z in NumPy on the host.  No GPU, no number: it fails without one.
+
+    python tools/detect_bench.py --null [--repeats 5]
+
+The false-alarm calibration: detect_null.DetectNull.run(R) beside
+Detect.fold_rows of S samples at the same shape, alternating, for 64x64 2-source oversample 1
+(R = 4096), 128x128 3-source oversample 1 (R = 1024) and 64x64 oversample 4 (R = 1024).  One
+JSON line per case: the time per realisation and per sample, their ratio (a realisation does
+half a sample's FMAs and builds no table: the bound is 0.5), the realisations' FP64 rate from
+G n^2 lane-FMAs each as a fraction of the vector peak (the whole run: noise, weighting,
+correlation, reductions and the results' copy), and the time per realisation of the same maps
+as one dense product in NumPy on the host.  The kernels' shares of a batch come from a kernel
+trace of this run (rocprofv3 --kernel-trace --stats).
 """
 import argparse
 import json
@@ -51,12 +63,61 @@ def host_one(n):
     return time.perf_counter() - t
 
 
+def host_null(n, R=32):
+    """R realisations' correlations as one dense product on the host, per realisation."""
+    rng = np.random.RandomState(0)
+    K, y = rng.uniform(size=(n * n, n * n)), rng.normal(size=(n * n, R))
+    t = time.perf_counter()
+    K @ y
+    return (time.perf_counter() - t) / R
+
+
+def null_bench(repeats):
+    from olpefit_amd import synth
+    from olpefit_amd.core import Sampler
+    from olpefit_amd.detect import Detect
+    from olpefit_amd.detect_null import DetectNull
+
+    def timed_null(h, R):
+        h.reset()
+        t = time.perf_counter()
+        h.run(R)
+        h.results()
+        return time.perf_counter() - t
+    for n, nsrc, os_, R, S in ((64, 2, 1, 4096, 4096), (128, 3, 1, 1024, 512),
+                               (64, 2, 4, 1024, 512)):
+        img, truth = synth.make_image(n, nsrc, 0)
+        rows = rows_about(truth, S, 1)
+        with Sampler(img, 1.0, 1, 1, 2, nsrc=nsrc) as s, \
+                Detect(s, pivot=truth, oversample=os_) as d, DetectNull(d, truth) as h:
+            timed(d, rows[:256]), timed_null(h, 64)
+            td, tn = [], []
+            for _ in range(repeats):
+                td.append(timed(d, rows))
+                tn.append(timed_null(h, R))
+        G = float(os_ * (n - 1) + 1) ** 2
+        per_r, per_s = float(np.median(tn)) / R, float(np.median(td)) / S
+        print(json.dumps({
+            "null": True, "side": n, "nsrc": nsrc, "oversample": os_, "realisations": R,
+            "samples": S, "repeats": repeats, "null_s_median": float(np.median(tn)),
+            "null_s_min": float(min(tn)), "detect_s_median": float(np.median(td)),
+            "s_per_realisation": per_r, "s_per_sample": per_s,
+            "ratio_realisation_to_sample": per_r / per_s,
+            "fp64_peak_fraction": G * n * n / per_r / PEAK_FMA,
+            "host_numpy_s_per_realisation": host_null(n) if n <= 64 and os_ == 1 else None}),
+            flush=True)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--null", action="store_true",
+                    help="the false-alarm calibration beside the detection fold")
     ap.add_argument("--samples", type=int, nargs="+", default=[4096, 65536])
     ap.add_argument("--big", type=int, default=1024, help="samples of the 128x128 case (0: skip)")
     ap.add_argument("--repeats", type=int, default=5)
     args = ap.parse_args(argv)
+    if args.null:
+        return null_bench(args.repeats)
     from olpefit_amd import synth
     from olpefit_amd.core import Sampler
     from olpefit_amd.detect import Detect
